@@ -7,6 +7,17 @@ complex FIR @1/2/4/8 GPU; % HBM roofline".  One step = one device-resident
 FIRFilter::execute_block pass (overlap-save kernel) over the whole channel.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5] [--log2n 30] [--algo fft|exact|fma]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set-up, the settle
+and warm-up steps, the K timed steps, the result line.  `--dump-outputs DIR`
+also writes what the last timed step computed (DIR/out.npy, see dump_outputs).
+`--full` adds everything else the script measures or checks: the copy-bandwidth
+measurement (`roofline.stream_copy_GBps`), the parity check against the
+restatement (exit status 3 when it fails), with more than one rank or `--dist`
+the RCCL gather and its check, config 2's drop-in cost figures and the CPU
+baseline; `--no-cpu`, `--no-parity`, `--no-gather` and `--no-dropin` take single
+parts out of a `--full` run.
 
 Other configs (BASELINE.json configs[2..4]):
   3  4-biquad cascade (scipy butter(8, 0.2) SOS), real f32, 1 GiS, block-parallel scan
@@ -22,8 +33,8 @@ SURVEY §8f rows (build-defined cases, same parity + measurement fields):
  12  Normal DF-II IIR, order 2, real f32, 2^30 samples (dense-system wave scan)
 
 With N ranks each rank processes its own independent channel(s) (weak
-scaling, no collective in the timed region); RCCL is used afterwards only for
-the final gather of every rank's whole output to rank 0, timed separately
+scaling, no collective in the timed region); with `--full` RCCL is used afterwards
+for the final gather of every rank's whole output to rank 0, timed separately
 (`gather`) and checked there against the f64 restatement.  rank 0 prints one
 JSON line.  `--gpus N` under torch.distributed.run must equal WORLD_SIZE;
 without a torchrun environment this script (never touching the GPU itself)
@@ -55,15 +66,24 @@ def parse():
     p.add_argument("--config", type=int, default=2, choices=list(range(1, 13)))
     p.add_argument("--log2n", type=int, default=30, help="samples per GPU per step (configs 2-4)")
     p.add_argument("--algo", default="fft", choices=["fft", "exact", "fma"], help="config 2 kernel")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the output of the last timed step to DIR/out.npy (out_rank<r>.npy on rank r > 0): "
+                        "float32 / float64, complex samples as (re, im) pairs; a fixed, seeded sample of an output "
+                        "larger than 32 MiB")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the copy-bandwidth measurement, the parity "
+                        "check, the RCCL gather and its check (ranks > 1 or --dist), config 2's drop-in costs and "
+                        "the CPU baseline")
     p.add_argument("--cpu-samples", type=int, default=None,
                    help="bounded sample of the same workload timed on the host (oracle restatement)")
-    p.add_argument("--no-cpu", action="store_true")
-    p.add_argument("--no-parity", action="store_true")
-    p.add_argument("--no-gather", action="store_true", help="skip the final RCCL gather of every rank's output")
+    p.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    p.add_argument("--no-parity", action="store_true", help="--full without the parity checks")
+    p.add_argument("--no-gather", action="store_true",
+                   help="--full without the final RCCL gather of every rank's output")
     p.add_argument("--dist", action="store_true",
-                   help="run the multi-GPU code path (RCCL process group, barriers, max-over-ranks, the final "
-                        "gather and its check) even at world size 1: the RCCL path on a one-GPU box")
-    p.add_argument("--no-dropin", action="store_true", help="config 2: skip the drop-in cost figures")
+                   help="run the multi-GPU code path (RCCL process group, barriers, max-over-ranks and, with "
+                        "--full, the final gather and its check) even at world size 1: the RCCL path on one GPU")
+    p.add_argument("--no-dropin", action="store_true", help="--full, config 2: without the drop-in cost figures")
     p.add_argument("--shard", default="channel", choices=["channel", "time"],
                    help="configs 2 and 4: independent channels per rank (default), or one long stream "
                         "time-sharded (rank r filters inputs [r n, (r+1) n) after an (L-1)-input halo)")
@@ -144,6 +164,34 @@ def settle(w, stream, torch, ms=150.0, chunk=8):
         # every rank runs the same number of steps (a step may hold a collective: cfg3 --shard time)
         if P.max_over_ranks(float(t < ms), device="cuda") == 0.0:
             return {"steps": n, "ms": round(t, 1)}
+
+
+DUMP_MAX_BYTES = 32 << 20  # all ranks together
+DUMP_EDGE = 4096
+
+
+def dump_outputs(path, out, torch, world=1):
+    """Write the device tensor `out` (what a caller of the timed path holds after the last
+    timed step) to `path` as a float32 / float64 .npy; complex samples become (re, im) rows.
+    An output above DUMP_MAX_BYTES / world is sampled at positions that depend only on its length:
+    the first and last DUMP_EDGE elements and, between them, sorted draws of
+    default_rng(SEED).  The same arguments therefore give files that compare element by
+    element between two builds."""
+    flat = out.reshape(-1)
+    n = flat.numel()
+    keep = DUMP_MAX_BYTES // world // flat.element_size()
+    if n > keep:
+        mid = np.sort(np.random.default_rng(SEED).integers(DUMP_EDGE, n - DUMP_EDGE, keep - 2 * DUMP_EDGE))
+        idx = np.concatenate([np.arange(DUMP_EDGE), mid, np.arange(n - DUMP_EDGE, n)])
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    if flat.is_complex():
+        flat = torch.view_as_real(flat)
+    a = flat.cpu().numpy()
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64)
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    np.save(path, a)
+    return {"file": path, "shape": list(a.shape), "dtype": str(a.dtype), "of_elements": n}
 
 
 def timed_cpu(run_chunk, label, samples, chunk, cores=1):
@@ -1232,6 +1280,8 @@ def main():
         sys.exit(spawn_ranks(args.gpus))
     if args.gpus is not None and args.gpus != world:
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be at least 1 and --warmup at least 0")
     if args.shard == "time" and args.config not in (2, 3, 4):
         sys.exit("bench.py: --shard time applies to configs 2 (FIR), 3 (IIR) and 4 (decimator)")
     if args.dry_run:
@@ -1258,10 +1308,10 @@ def main():
         name, val = kv.split("=")
         w.f.set_tuning(getattr(sd._lib, "TUNE_" + name.upper()), int(val))
     torch.cuda.synchronize()
-    # achievable copy bandwidth of this box, measured before the warm-up: it also
-    # brings the device out of its idle clocks (~0.3 s of streaming) so the
-    # workload's own warm-up steps are not spent on the clock ramp
-    copy_gbps = stream_copy_gbps(torch, sd)
+    # --full: achievable copy bandwidth of this box (~0.3 s of streaming), measured before
+    # the warm-up; the settle steps bring the device out of its idle clocks with or
+    # without it
+    copy_gbps = stream_copy_gbps(torch, sd) if args.full else None
     settled = settle(w, stream, torch, ms=args.settle_ms) if args.settle_ms > 0 else None
 
     for _ in range(args.warmup):
@@ -1285,10 +1335,17 @@ def main():
     ev_ms = [s.elapsed_time(e) for s, e in zip(starts, ends)]
     wall = P.max_over_ranks(wall, device="cuda")  # the job runs as long as its slowest rank
 
-    # final gather over RCCL (timed separately, not part of `value`): every rank's
+    # what the last timed step left in the caller's output buffer, before anything below reuses it
+    dumped = None
+    if args.dump_outputs:
+        name = "out.npy" if rank == 0 else f"out_rank{rank}.npy"
+        dumped = dump_outputs(os.path.join(args.dump_outputs, name), w.output() if hasattr(w, "output") else w.d_out,
+                              torch, world)
+
+    # --full: final gather over RCCL (timed separately, not part of `value`): every rank's
     # whole output to rank 0, checked there against the f64 restatement
     gather = None
-    if use_dist and not args.no_gather:
+    if args.full and use_dist and not args.no_gather:
         piece = w.output() if hasattr(w, "output") else w.d_out
         torch.cuda.synchronize()
         dist.barrier()
@@ -1305,7 +1362,7 @@ def main():
         torch.cuda.empty_cache()
 
     parity = None
-    if not args.no_parity and rank == 0:
+    if args.full and not args.no_parity and rank == 0:
         parity = w.parity(stream, np.random.default_rng(1))
 
     if rank == 0:
@@ -1343,15 +1400,19 @@ def main():
                          "kernel_ms": round(kern_ms, 4), "kernel_ms_median": round(float(np.median(ev_ms)), 4),
                          "kernel_ms_min": round(float(np.min(ev_ms)), 4),
                          "algorithmic_bytes_per_launch": w.bytes_per_step,
-                         "stream_copy_GBps": round(copy_gbps, 1), "frac_of_stream_copy": round(achieved / copy_gbps, 4)},
+                         "stream_copy_GBps": copy_gbps and round(copy_gbps, 1),
+                         "frac_of_stream_copy": copy_gbps and round(achieved / copy_gbps, 4)},
             "parity": {"check": getattr(w, "parity_check", "rel_rms vs the f64 restatement"),
-                       "value": parity, "tolerance": tol, "ok": parity_ok},
+                       "value": parity, "tolerance": tol, "ok": parity_ok if args.full else None},
             "gather": gather,
+            "full": args.full,
         }
-        # the drop-in costs and the CPU baseline belong to the single-GPU line (rank 0 at N = 1)
-        if args.config == 2 and not args.no_dropin and world == 1:
+        if dumped:
+            out["outputs"] = dumped
+        # --full: the drop-in costs and the CPU baseline belong to the single-GPU line (rank 0 at N = 1)
+        if args.full and args.config == 2 and not args.no_dropin and world == 1:
             out["dropin"] = dropin_costs(torch, sd, w.h)
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             cb = w.cpu(args.cpu_samples or CPU_DEFAULT[args.config])
             cb["host_nproc"] = os.cpu_count()
             cb["host_affinity_cpus"] = len(os.sched_getaffinity(0))

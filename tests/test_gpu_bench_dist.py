@@ -1,5 +1,5 @@
 """The multi-GPU code path of bench.py on the MI355X (the RCCL path had only run
-over gloo on the CPU).  `bench.py --dist` runs a world of one rank through exactly the code the
+over gloo on the CPU).  `bench.py --dist --full` runs a world of one rank through exactly the code the
 driver's N-GPU runs take -- `init_process_group("nccl")`, the barriers around the timed region,
 the all_reduce MAX of the wall time, the chunked RCCL gather of the whole output into rank 0
 (`parallel.gather_full_to_root`, complex outputs as interleaved real pairs) and the gathered
@@ -25,7 +25,7 @@ def test_bench_rccl_path_one_rank(config, extra):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--dist", "--config", str(config),
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--dist", "--full", "--config", str(config),
                         "--steps", "2", "--warmup", "1", "--no-cpu", "--no-dropin", "--settle-ms", "0"] + extra,
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -29,10 +29,10 @@ for s in ${STEPS:-pytest}; do
         fftlab) run fftlab 300 python -u tools/fft_lab.py ;;
         nocopy*) run "$s" 300 python -u tools/steady_probe.py --config "${s#nocopy}" --steps 400 --no-copy ;;
         steady*) run "$s" 300 python -u tools/steady_probe.py --config "${s#steady}" --steps 400 ;;
-        bench) run bench 300 python -u bench.py --steps 20 --warmup 5 ${BENCH_ARGS:-} ;;
-        bench_cfg*) run "$s" 300 python -u bench.py --config "${s#bench_cfg}" --steps 20 --warmup 5 --no-cpu ;;
+        bench) run bench 300 python -u bench.py --full --steps 20 --warmup 5 ${BENCH_ARGS:-} ;;
+        bench_cfg*) run "$s" 300 python -u bench.py --full --config "${s#bench_cfg}" --steps 20 --warmup 5 --no-cpu ;;
         # tune8_<NAME>_<VALUE>: config 8 with one kernel-variant knob
-        tune8_*) t=${s#tune8_}; run "$s" 300 python -u bench.py --config 8 --steps 20 --warmup 5 --no-cpu \
+        tune8_*) t=${s#tune8_}; run "$s" 300 python -u bench.py --full --config 8 --steps 20 --warmup 5 --no-cpu \
                      --tune "${t%_*}=${t##*_}" ;;
         *) echo "unknown step $s"; exit 2 ;;
     esac

@@ -44,13 +44,13 @@ for s in ${STEPS:-pytest}; do
         fftlab) run fftlab 300 python -u tools/fft_lab.py ;;
         nocopy*) run "$s" 300 python -u tools/steady_probe.py --config "${s#nocopy}" --steps 400 --no-copy ;;
         steady*) run "$s" 300 python -u tools/steady_probe.py --config "${s#steady}" --steps 400 ;;
-        bench) run bench 300 python -u bench.py --steps 20 --warmup 5 ${BENCH_ARGS:-} ;;
+        bench) run bench 300 python -u bench.py --full --steps 20 --warmup 5 ${BENCH_ARGS:-} ;;
         # bench_tune_<NAME>_<VALUE>: the default config with one tuning key (e.g. bench_tune_OLS_KERNEL_3)
-        bench_tune_*) t=${s#bench_tune_}; run "$s" 300 python -u bench.py --steps 20 --warmup 5 --no-cpu \
+        bench_tune_*) t=${s#bench_tune_}; run "$s" 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu \
                      --tune "${t%_*}=${t##*_}" ${BENCH_ARGS:-} ;;
-        bench_cfg*) run "$s" 300 python -u bench.py --config "${s#bench_cfg}" --steps 20 --warmup 5 --no-cpu ;;
+        bench_cfg*) run "$s" 300 python -u bench.py --full --config "${s#bench_cfg}" --steps 20 --warmup 5 --no-cpu ;;
         # tune8_<NAME>_<VALUE>: config 8 with one kernel-variant knob
-        tune8_*) t=${s#tune8_}; run "$s" 300 python -u bench.py --config 8 --steps 20 --warmup 5 --no-cpu \
+        tune8_*) t=${s#tune8_}; run "$s" 300 python -u bench.py --full --config 8 --steps 20 --warmup 5 --no-cpu \
                      --tune "${t%_*}=${t##*_}" ;;
         # clock_cfg<N>: effective clock (GRBM_GUI_ACTIVE / 8 / wall) and SQ instruction counts of the
         # bench's sustained dispatches, one PMC pass (tools/clock_summary.py)

@@ -26,7 +26,7 @@ for step in "$@"; do
     iirtests) run iirtests 400 python -u -m pytest tests/test_gpu_iir.py -x -q --timeout 120 --timeout-method thread -p no:cacheprovider || exit $?;;
     libab) OLD=${OLD:-tools/_build/libsdsp_old.so} CONFIGS="${AB_CONFIGS:-3 12}" REPS=${REPS:-3} run libab 900 bash tools/lib_ab.sh ${TAG}_ab || exit $?;;
     gputests) run gputests 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider || exit $?;;
-    bench) run bench 300 python bench.py --steps 20 --warmup 5 || exit $?;;
+    bench) run bench 300 python bench.py --full --steps 20 --warmup 5 || exit $?;;
     *) echo "unknown step $step"; exit 2;;
   esac
 done

@@ -13,7 +13,7 @@ run() { local name=$1; local lim=$2; shift 2; timeout -k 10 $lim "$@" > gpurun_o
 declare -A KERN=([1]=fir_direct [2]="fir_ols_os_kernel<true, false, false>" [3]=sos_wscan [4]=decim_poly [5]=chan1024 [6]=acorr_pipe [7]=nco_mix [8]=fft1024_pipe [9]=agc_pipe [10]=interp_tile [11]=sos_serial [12]=sos_wscan)
 if [ -z "$SKIP_TESTS" ]; then run pytest 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider; fi
 for c in ${CONFIGS:-2 3 4 5}; do
-  run bench_cfg$c 300 python bench.py --config $c --steps 20 --warmup 5
+  run bench_cfg$c 300 python bench.py --full --config $c --steps 20 --warmup 5
   run prof_cfg$c 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${TAG}_prof_cfg$c -o run -- python bench.py --config $c --steps 20 --warmup 5 --no-cpu --no-parity --no-dropin
   python tools/prof_summary.py gpurun_out/${TAG}_prof_cfg$c "${KERN[$c]}" --last 20 --out gpurun_out/${TAG}_kernel_timed_cfg$c.json > /dev/null 2>&1 || echo "prof_summary cfg$c failed"
   if [ -z "$SKIP_PMC" ]; then

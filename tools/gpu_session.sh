@@ -9,5 +9,7 @@ ok $rc || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/s1_smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -5 gpurun_out/s1_smoke.log
 ok $rc || exit $rc
-timeout -k 10 300 python bench.py --steps 5 --warmup 2 --cpu-samples 2000000 > gpurun_out/s1_bench.log 2>&1
-rc=$?; echo "bench rc=$rc"; tail -5 gpurun_out/s1_bench.log
+BENCH_LOG=${BENCH_LOG:-bench_logs/s1_bench.log}
+mkdir -p "$(dirname "$BENCH_LOG")"
+timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --cpu-samples 2000000 > "$BENCH_LOG" 2>&1
+rc=$?; echo "bench rc=$rc"; tail -5 "$BENCH_LOG"

@@ -14,7 +14,7 @@ for c in ${CONFIGS:-2}; do
 import runpy, sys
 import solid_dsp_amd._lib as L
 L.LIB_PATH = '$lib'
-sys.argv = ['bench.py', '--config', '$c', '--steps', '20', '--warmup', '5', '--no-cpu', '--no-parity']
+sys.argv = ['bench.py', '--full', '--config', '$c', '--steps', '20', '--warmup', '5', '--no-cpu', '--no-parity']
 runpy.run_path('bench.py', run_name='__main__')" > gpurun_out/${TAG}_cfg${c}_r${r}_$b.log 2>&1 || exit 9
       python -c "
 import json
