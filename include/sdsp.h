@@ -324,8 +324,9 @@ SDSP_API int sdsp_iir_synchronize(sdsp_iir* h);
 /* ------------------------------------------------------------------------
  * FFT  (FFT::new / FFT::execute, src/fft/mod.rs:175-215).  direction: 0 FORWARD,
  * 1 REVERSE (unnormalised, like the reference).  precision: 0 = complex f32,
- * 1 = complex f64.  Sizes 1 .. 2^24, every size the reference plans (SURVEY §8f
- * row 2).  Power-of-two sizes up to 4096 run a radix-4 Stockham FFT in LDS, larger
+ * 1 = complex f64.  Sizes 1 .. 2^23 and the power of two 2^24;
+ * any other size fails with SDSP_E_INVALID_ARGUMENT: a size that is no power of
+ * two convolves at the power of two >= 2 nfft - 1, at most 2^24.  Power-of-two sizes up to 4096 run a radix-4 Stockham FFT in LDS, larger
  * powers of two a four-step FFT (two strided LDS passes, f64 inter-pass twiddles);
  * other sizes up to 512 a direct DFT, larger ones Bluestein's chirp-z transform
  * over a power-of-two convolution (where the reference plans Rader / mixed radix,

@@ -1,5 +1,6 @@
 //! `solid::fft` (src/fft/mod.rs:15-215): FFT::new / FFT::execute on the device
-//! (every size the reference plans; unnormalised REVERSE like the reference).
+//! (sizes 1 ..= 2^23 and the power of two 2^24, see include/sdsp.h; unnormalised
+//! REVERSE like the reference).
 //! The public enums and the error type are the reference's (mod.rs:16-55,
 //! 145-161); the plan itself is the device's (include/sdsp.h sdsp_fft_*), so
 //! `FFTMethod` records the reference planner's choice (mod.rs:123-143) for

@@ -94,23 +94,27 @@ fft_pow2_kernel(const c2<T>* __restrict__ x, c2<T>* __restrict__ y, const c2<T>*
         for (int i = lane; i < N; i += nthr) y[tr * N + i] = r[i];
 }
 
-// direct DFT for sizes that are not powers of two: one thread per output bin
+// direct DFT for sizes that are not powers of two: one thread per output bin, the
+// batch * N bins of every transform walked with a grid stride (any batch launches)
 template <typename T, bool INV>
 __global__ void __launch_bounds__(256)
 dft_direct_kernel(const c2<T>* __restrict__ x, c2<T>* __restrict__ y, const c2<T>* __restrict__ tw, int N,
                   long long batch) {
-    const long long tr = blockIdx.y;
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (tr >= batch || k >= N) return;
-    const c2<T>* xi = x + tr * N;
-    c2<T> acc = {T(0), T(0)};
-    int m = 0;  // (n k) mod N, advanced incrementally
-    for (int n = 0; n < N; ++n) {
-        acc = ca(acc, cm(xi[n], twl<T, INV>(tw, m)));
-        m += k;
-        if (m >= N) m -= N;
+    const long long total = batch * N;
+    for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < total;
+         o += (long long)gridDim.x * blockDim.x) {
+        const long long tr = o / N;
+        const int k = (int)(o - tr * N);
+        const c2<T>* xi = x + tr * N;
+        c2<T> acc = {T(0), T(0)};
+        int m = 0;  // (n k) mod N, advanced incrementally
+        for (int n = 0; n < N; ++n) {
+            acc = ca(acc, cm(xi[n], twl<T, INV>(tw, m)));
+            m += k;
+            if (m >= N) m -= N;
+        }
+        y[o] = acc;
     }
-    y[tr * N + k] = acc;
 }
 
 // channeliser: block (frame m, stream s); M = N power of two
@@ -307,7 +311,9 @@ hipError_t launch_fft_t(const FftArgs& a, hipStream_t s) {
             hipLaunchKernelGGL((fft_pow2_kernel<T, false>), grid, dim3(nthr * tpb), lds, s, (const c2<T>*)a.x,
                                (c2<T>*)a.y, (const c2<T>*)a.tw, N, a.logN, (long long)a.batch, nthr, tpb);
     } else {
-        dim3 grid((unsigned)((N + 255) / 256), (unsigned)a.batch);
+        long long blocks = ((long long)a.batch * N + 255) / 256;
+        if (blocks > 65536) blocks = 65536;
+        dim3 grid((unsigned)blocks);
         if (a.inverse)
             hipLaunchKernelGGL((dft_direct_kernel<T, true>), grid, dim3(256), 0, s, (const c2<T>*)a.x, (c2<T>*)a.y,
                                (const c2<T>*)a.tw, N, (long long)a.batch);

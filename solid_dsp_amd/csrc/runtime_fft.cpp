@@ -212,6 +212,12 @@ int sdsp_fft_create(sdsp_fft** out, size_t nfft, int direction, int precision, i
         set_error("FFT size must be in [1, 2^24]");
         return SDSP_E_INVALID_ARGUMENT;
     }
+    // Bluestein convolves at M = the power of two >= 2 nfft - 1: above 2^23 that is 2^25, whose
+    // four-step passes would be longer than the 4096 points fft_pass_kernel holds in LDS
+    if (!is_pow2(nfft) && nfft > (1u << 23)) {
+        set_error("FFT sizes above 2^23 must be powers of two (the chirp-z convolution is at most 2^24 points)");
+        return SDSP_E_INVALID_ARGUMENT;
+    }
     if (direction != 0 && direction != 1) return SDSP_E_INVALID_ARGUMENT;
     int st = check_gfx950(device);
     if (st) return st;

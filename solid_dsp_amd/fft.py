@@ -1,7 +1,8 @@
 """``solid::fft`` on MI355X (src/fft/mod.rs:175-215).
 
 ``FFT(nfft, FFTDirection.FORWARD).execute(x)`` is ``FFT::new(nfft, FORWARD,
-ESTIMATE).execute(&x)``: unnormalised in both directions, any size 1 .. 2^24.
+ESTIMATE).execute(&x)``: unnormalised in both directions, any size 1 .. 2^23
+and the power of two 2^24 (other sizes above 2^23 raise ``SdspError``).
 The device runs a radix-4 Stockham FFT in LDS (powers of two up to 4096), a
 four-step FFT (larger powers of two), a direct DFT (other sizes up to 512) or
 Bluestein's chirp-z transform (other sizes).

@@ -33,6 +33,13 @@ def rel_rms(y, ref):
     return float(np.linalg.norm(y - ref) / max(np.linalg.norm(ref), 1e-300))
 
 
+def rel_rms_rows(y, ref):
+    """rel_rms of every row of a [rows, n] pair on its own (one figure per transform)."""
+    y = np.asarray(y, dtype=np.complex128)
+    ref = np.asarray(ref, dtype=np.complex128)
+    return np.linalg.norm(y - ref, axis=-1) / np.maximum(np.linalg.norm(ref, axis=-1), 1e-300)
+
+
 def bits_equal(a, b):
     a = np.ascontiguousarray(a)
     b = np.ascontiguousarray(b)
