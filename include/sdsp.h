@@ -65,7 +65,8 @@ typedef enum {
     SDSP_ALGO_EXACT = 1, /* direct form in the reference summation order, no FMA contraction:
                             bit-identical to the reference algorithm at the handle's precision */
     SDSP_ALGO_FMA = 2,   /* direct form, same order, fused multiply-add                      */
-    SDSP_ALGO_FFT = 3    /* overlap-save fast convolution (N = 4096) in LDS                  */
+    SDSP_ALGO_FFT = 3    /* overlap-save fast convolution (N = 4096) in LDS: 32-bit complex samples,
+                            and real f32 samples with real f32 taps (two real segments per transform) */
 } sdsp_algo;
 
 typedef enum {
@@ -160,7 +161,9 @@ typedef enum {
                                     compiled in when L <= 257), the boundary segments and the next history
                                     in a second,
                                     1 persistent packed kernel for the interior segments (L <= 1025),
-                                    2 scalar kernel, 3 the one-shot kernel with 16-byte lanes */
+                                    2 scalar kernel, 3 the one-shot kernel with 16-byte lanes.
+                                    Real f32 handles: 0 (default, and every value but 3) 4-byte lanes,
+                                    3 8-byte lanes (8-byte aligned rows, else as 0) */
     SDSP_TUNE_CHAN_XCD_ORDER = 15, /* streaming channeliser: 1 (default) = each XCD walks a contiguous
                                      eighth of the frame chunks, 0 = launch order */
     SDSP_TUNE_HOST_STEP = 16,     /* FIR / decimator: 1 (default) = execute(sample), push and host blocks with

@@ -30,7 +30,7 @@ pub fn default_algorithm() -> i32 {
 
 /// FIRFilter / DecimatingFIRFilter on the device
 pub trait FirDevice {
-    /// SDSP_ALGO_EXACT (default, bit-identical), SDSP_ALGO_FMA, SDSP_ALGO_FFT (c32 FIR), SDSP_ALGO_AUTO
+    /// SDSP_ALGO_EXACT (default, bit-identical), SDSP_ALGO_FMA, SDSP_ALGO_FFT (c32 and real f32 FIR), SDSP_ALGO_AUTO
     fn set_algorithm(&mut self, algo: i32) -> Result<(), Box<dyn Error>>;
     /// per-sample calls and short host blocks on the host (true, default) or as device launches
     fn set_host_step(&mut self, on: bool);

@@ -340,6 +340,14 @@ hipError_t launch_fir_ols(const OlsPlan& p, const void* x, const void* hist, voi
                           int L, size_t channels, int num_cus, hipStream_t s, bool* hist_done) {
     *hist_done = false;
     if (n == 0) return hipSuccess;
+    if (p.sample_bytes == 4) {
+        // real f32: the packed-pair kernel for every segment, with the history update (n >= L - 1)
+        const bool fused_hist = n >= (size_t)(L - 1);
+        hipError_t e = launch_fir_ols_real(p, x, hist, fused_hist ? new_hist : nullptr, y, n, L - 1, channels, s,
+                                           p.kernel == kOlsOneShotWide);
+        if (e == hipSuccess) *hist_done = fused_hist;
+        return e;
+    }
     const int h2 = p.halo_rows;
     const long long V = 4096 - 256 * h2;
     const long long nseg = ((long long)n + V - 1) / V;

@@ -159,8 +159,12 @@ int fir_alloc_state(sdsp_fir* h) {
     return SDSP_OK;
 }
 
+// real f32 samples with real f32 taps run the packed-pair kernel (kern_fir_ols_real.hip)
+bool ols_real(const sdsp_fir* h) { return h->dtype == SDSP_RR32; }
+
 bool ols_applicable(const sdsp_fir* h) {
-    return (h->dtype == SDSP_RC32 || h->dtype == SDSP_CC32) && h->M == 1 && h->L >= 2 && h->L - 1 <= 256 * 15;
+    return (h->dtype == SDSP_RR32 || h->dtype == SDSP_RC32 || h->dtype == SDSP_CC32) && h->M == 1 && h->L >= 2 &&
+           h->L - 1 <= 256 * 15;
 }
 
 // spectrum of g[i] = scale * h[L-1-i] in the lane layout of kern_fir_ols.hip
@@ -208,12 +212,18 @@ int ols_build(sdsp_fir* h) {
             tw2[2 * (a * 16 + b)] = (float)std::cos(-2.0 * M_PI * ph / 256.0);
             tw2[2 * (a * 16 + b) + 1] = (float)std::sin(-2.0 * M_PI * ph / 256.0);
         }
-    SDSP_TRY(h->d_H.ensure(Hs.size() * 4), "alloc H");
-    SDSP_TRY(h->d_tw1.ensure(tw1.size() * 4), "alloc tw1");
-    SDSP_TRY(h->d_tw2.ensure(tw2.size() * 4), "alloc tw2");
-    SDSP_TRY(hipMemcpyAsync(h->d_H.p, Hs.data(), Hs.size() * 4, hipMemcpyHostToDevice, h->stream), "copy H");
-    SDSP_TRY(hipMemcpyAsync(h->d_tw1.p, tw1.data(), tw1.size() * 4, hipMemcpyHostToDevice, h->stream), "copy tw1");
-    SDSP_TRY(hipMemcpyAsync(h->d_tw2.p, tw2.data(), tw2.size() * 4, hipMemcpyHostToDevice, h->stream), "copy tw2");
+    // real f32 samples: the packed-pair kernel reads d_pkt and d_ostab only
+    const bool real = ols_real(h);
+    if (!real) {
+        SDSP_TRY(h->d_H.ensure(Hs.size() * 4), "alloc H");
+        SDSP_TRY(h->d_tw1.ensure(tw1.size() * 4), "alloc tw1");
+        SDSP_TRY(h->d_tw2.ensure(tw2.size() * 4), "alloc tw2");
+        SDSP_TRY(hipMemcpyAsync(h->d_H.p, Hs.data(), Hs.size() * 4, hipMemcpyHostToDevice, h->stream), "copy H");
+        SDSP_TRY(hipMemcpyAsync(h->d_tw1.p, tw1.data(), tw1.size() * 4, hipMemcpyHostToDevice, h->stream),
+                 "copy tw1");
+        SDSP_TRY(hipMemcpyAsync(h->d_tw2.p, tw2.data(), tw2.size() * 4, hipMemcpyHostToDevice, h->stream),
+                 "copy tw2");
+    }
     // the same tables for the packed kernel, k-pair major so that a table load is one
     // coalesced 16-byte access per lane: float4 (p, i) = entries 2p, 2p + 1 of row i;
     // [0, 2048): H rows t, [2048, 4096): tw1 rows, [4096, 4224): tw2 rows
@@ -272,7 +282,7 @@ int ols_build(sdsp_fir* h) {
     // float4 [p][i] = {H(i, 2p), H(i, 2p + 1)} for p < 4, H(i, k2) = G[k0 + 16 k1 + 256 k2] of
     // lane i = 16 k0 + k1; entry i = 256 is the mirror of lane (0, 0), whose bins k2 >= 8 mirror
     // k2' = 16 - k2 (k2' = 8 included): stored so that the kernel's conj-and-swap yields them
-    const bool real_taps = !coef_is_complex(h->dtype);
+    const bool real_taps = !coef_is_complex(h->dtype) && !real;  // (the lab's c32 kernels only)
     if (real_taps) {
         std::vector<float> hh(4 * 4 * kOlsHalfRow);
         auto set = [&](int q, int i, int half, cd v) {
@@ -299,9 +309,10 @@ int ols_build(sdsp_fir* h) {
     SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
     h->ols = OlsPlan{};
     h->ols.d_hhalf = real_taps ? h->d_hhalf.p : nullptr;
-    h->ols.d_H = h->d_H.p;
-    h->ols.d_tw1 = h->d_tw1.p;
-    h->ols.d_tw2 = h->d_tw2.p;
+    h->ols.d_H = real ? nullptr : h->d_H.p;
+    h->ols.d_tw1 = real ? nullptr : h->d_tw1.p;
+    h->ols.d_tw2 = real ? nullptr : h->d_tw2.p;
+    h->ols.sample_bytes = real ? 4 : 8;
     h->ols.halo_rows = h2;
     h->ols.kernel = h->ols_kernel;
     h->ols.d_pkt = h->d_pkt.p;
@@ -314,7 +325,8 @@ int fir_resolve_algo(const sdsp_fir* h, size_t n) {
     if (h->algo == SDSP_ALGO_FFT) return ols_applicable(h) ? SDSP_ALGO_FFT : SDSP_ALGO_EXACT;
     if (h->algo != SDSP_ALGO_AUTO) return h->algo;
     // AUTO: overlap-save for long 32-bit complex blocks, reference-order direct form otherwise
-    if (ols_applicable(h) && n >= (size_t)(1 << 16)) return SDSP_ALGO_FFT;
+    // (real f32 streams take overlap-save only when asked: AUTO keeps their bits)
+    if (ols_applicable(h) && !ols_real(h) && n >= (size_t)(1 << 16)) return SDSP_ALGO_FFT;
     return SDSP_ALGO_EXACT;
 }
 // AUTO on a decimating handle: the fused multiply-add kernels for long 32-bit blocks (n inputs)
@@ -625,7 +637,7 @@ int sdsp_fir_set_channels(sdsp_fir* h, size_t channels) {
 int sdsp_fir_set_algo(sdsp_fir* h, int algo) {
     if (!h || algo < 0 || algo > 3) return SDSP_E_INVALID_ARGUMENT;
     if (algo == SDSP_ALGO_FFT && !ols_applicable(h)) {
-        set_error("overlap-save needs 32-bit complex samples, no decimation and L-1 <= 3840");
+        set_error("overlap-save needs 32-bit samples (complex, or real with real taps), no decimation and L-1 <= 3840");
         return SDSP_E_UNSUPPORTED;
     }
     h->algo = algo;

@@ -27,11 +27,12 @@ bool try_launch_decim_poly(int dtype, const FirArgs& a, hipStream_t s, hipError_
 hipError_t launch_hist_update(int dtype, const void* x, const void* old_hist, void* new_hist, size_t n, int Lm1,
                               size_t channels, hipStream_t s);
 
-// overlap-save (N = 4096) for 32-bit complex samples
+// overlap-save (N = 4096) for 32-bit complex samples and for real f32 samples with real taps
 constexpr int kOlsOneShot = 0;     // interior segments: one-shot XCD-ordered kernel (kern_fir_ols_os.hip)
 constexpr int kOlsPersistent = 1;  // persistent packed kernel, kOlsSegsPerBlock segments per workgroup
 constexpr int kOlsScalar = 2;      // scalar persistent kernel for every segment (kern_fir_ols.hip)
-constexpr int kOlsOneShotWide = 3;  // the one-shot kernel with 16-byte lanes (pair exchange by DPP)
+constexpr int kOlsOneShotWide = 3;  // the one-shot kernel with 16-byte lanes (pair exchange by DPP);
+                                    // real f32: 8-byte lanes, every other value the 4-byte default
 constexpr int kOlsSegsPerBlock = 16;
 // W4096 column bases [3][256], W256 row bases [3][16], then the first powers alone: {C1, D1}
 // per column [256] and {E1, F1} per row [16] (kern_fir_ols_os.hip, runtime.cpp ols_build)
@@ -51,6 +52,8 @@ struct OlsPlan {
     // real taps (conjugate-symmetric spectrum): the half-spectrum table of the one-shot kernel,
     // float4 [4][kOlsHalfRow] (runtime.cpp ols_build), else null
     void* d_hhalf = nullptr;
+    int sample_bytes = 8;  // 8: c32 samples; 4: real f32 samples and taps (kern_fir_ols_real.hip,
+                           // which reads d_pkt and d_ostab only)
 };
 constexpr int kOlsHalfRow = 257;  // 256 lanes + the tail entry of lane (0, 0)
 constexpr int kOlsN = 4096;
@@ -63,6 +66,9 @@ void ols_interior_range(long long n, int h2, long long* lo, long long* hi);
 // interior-segment kernels (16-byte rows)
 hipError_t launch_fir_ols_os(const OlsPlan& p, const void* x, const void* hist, void* new_hist, void* y, size_t n,
                              int Lm1, size_t channels, hipStream_t s, bool wide);
+// real f32 samples: pairs of segments packed as one complex segment (kern_fir_ols_real.hip)
+hipError_t launch_fir_ols_real(const OlsPlan& p, const void* x, const void* hist, void* new_hist, void* y, size_t n,
+                               int Lm1, size_t channels, hipStream_t s, bool lane8);
 hipError_t launch_fir_ols_pk(const OlsPlan& p, const void* x, void* y, size_t n, size_t channels, hipStream_t s,
                              long long lo, long long hi);
 
