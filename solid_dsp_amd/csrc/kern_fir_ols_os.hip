@@ -115,18 +115,24 @@ __device__ __forceinline__ void pair_exchange(f2 a, f2 b, f2& lo, f2& hi) {
 //   EDGE   the boundary segments of a call (launched apart, so the interior kernel carries no
 //          boundary code): past the end of the stream loads return 0 and stores are dropped, rows
 //          before it come from the history, and the call's last segment writes the next history.
+//
+// xw / yw point at the segment's window x[base, base + 4096) of its channel (the callers add the
+// segment's offset once, for both); base, n, hist, new_hist and Lm1 are read by EDGE only.
 template <bool HALO1, bool WIDE, bool EDGE>
-__device__ __forceinline__ void ols_os_segment(const f2* __restrict__ x, const f2* __restrict__ hist,
+__device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const f2* __restrict__ hist,
                                                f2* __restrict__ new_hist, const float4* __restrict__ Hs,
-                                               const float4* __restrict__ tb, f2* __restrict__ y, long long base,
+                                               const float4* __restrict__ tb, f2* __restrict__ yw, long long base,
                                                long long n, int Lm1, int h2, f2* img, int t) {
     const int hi4 = t >> 4, lo4 = t & 15;
     if constexpr (HALO1) h2 = 1;  // compiled in (the launcher checks h2 == 1)
-    // the segment's window x[base, base + 4096) as a raw buffer
-    const long long rem = n - base;
-    const int nrec = (!EDGE || rem >= 4096) ? 32768 : (int)(8 * rem);
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc((void*)(x + base), (short)0, nrec, kBufWord3);
-    const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)(y + base), (short)0, nrec, kBufWord3);
+    // the segment's window as a raw buffer
+    int nrec = 32768;
+    if constexpr (EDGE) {
+        const long long rem = n - base;
+        if (rem < 4096) nrec = (int)(8 * rem);
+    }
+    const auto rx = __builtin_amdgcn_make_buffer_rsrc((void*)xw, (short)0, nrec, kBufWord3);
+    const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)yw, (short)0, nrec, kBufWord3);
     const auto rt = __builtin_amdgcn_make_buffer_rsrc((void*)tb, (short)0, kOlsOsTabF4 * 16, kBufWord3);
     const auto rh = __builtin_amdgcn_make_buffer_rsrc((void*)Hs, (short)0, 2048 * 16, kBufWord3);
     // twiddle bases: {C1, D1} of column t and {E1, F1} of row lo4 (runtime.cpp ols_build), requested
@@ -170,9 +176,11 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ x, const f
 #pragma unroll
         for (int k = 0; k < 8; ++k) pair_exchange(f2{q[k].x, q[k].y}, f2{q[k].z, q[k].w}, v[k], v[8 + k]);
     } else {
-        // the rows in row order (the compiler interleaves them as 0, 4, 1, 5, 8, 12, 9, 13, ...):
-        // 2 % faster than the first radix-4 stage's order and than either order enforced with
-        // scheduling barriers (profiles/r05/lab/r05h_olsburst.log, r05i_olsburst.log)
+        // the rows in row order (behind the two table loads the compiler issues them as 0, 1, 4, 5,
+        // 8, 12, 9, 13, 2, 6, 10, 14, 3, 7, 11, 15): 2 % faster than the first radix-4 stage's order
+        // and than either order enforced with scheduling barriers (profiles/r05/lab/
+        // r05h_olsburst.log, r05i_olsburst.log); the issue order moves the time by 2-3 %, so it is
+        // read off the disassembly with every change to this prologue (profiles/r07/LAB.md)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             if (HALO1 && (r == 0 || r == 15))
@@ -267,28 +275,48 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ x, const f
 
 // Interior segments [lo, hi) of every channel (whole window inside the stream): workgroup b runs on
 // XCD b % 8 and takes segment lo + (b % 8) q + b / 8, so each XCD streams one contiguous eighth of
-// the call in order.  EDGE: the boundary segments [0, lo) and [hi, nseg) (block b takes segment
-// b < lo ? b : hi + b - lo), the last one writing the next history (new_hist).
+// the call in order.  The grid is 8 q wide, so b / 8 < q and the segment lies inside its XCD's
+// eighth; only the ragged end of the range (seg >= hi) has to be refused.
+//
+// The first row load waits for everything before it while the workgroup's slot moves no bytes,
+// so the start-up path is kept short: 12 argument dwords, ordered by first use, which the
+// translation unit is compiled to preload into SGPRs (csrc/Makefile; a fetch of the same list is
+// the compiler's fallback), and segment arithmetic in 32 bits on the scalar unit (the launcher
+// refuses 2^31 or more segments): no scalar-memory wait and no vector compare before the loads.
+// stride is the distance between channels in samples.
+template <bool HALO1, bool WIDE, bool EDGE>
+__global__ void __launch_bounds__(256, 4)
+fir_ols_os_kernel(const f2* __restrict__ x, f2* __restrict__ y, const float4* __restrict__ Hs,
+                  const float4* __restrict__ tb, long long stride, unsigned lo, unsigned hi, unsigned q, int h2) {
+    static_assert(!EDGE, "the boundary segments take the long argument list");
+    __shared__ __attribute__((aligned(16))) f2 img[16 * kRow];
+    const unsigned seg = lo + (blockIdx.x & 7u) * q + (blockIdx.x >> 3);
+    if (seg >= hi) return;  // uniform over the workgroup
+    if constexpr (HALO1) h2 = 1;
+    // window start in samples: seg V - 256 h2 >= 0 (lo >= 1), one 32 x 32 -> 64 multiply
+    const unsigned H = 256u * (unsigned)h2;
+    const long long off = (long long)((unsigned long long)seg * (4096u - H)) - (long long)H +
+                          (long long)blockIdx.y * stride;
+    ols_os_segment<HALO1, WIDE, false>(x + off, nullptr, nullptr, Hs, tb, y + off, 0, 0, 0, h2, img, threadIdx.x);
+}
+
+// The boundary segments [0, lo) and [hi, nseg) of every channel (block b takes segment
+// b < lo ? b : hi + b - lo), the last one writing the next history (new_hist): a launch of its
+// own, so the interior kernel carries none of this.
 template <bool HALO1, bool WIDE, bool EDGE>
 __global__ void __launch_bounds__(256, 4)
 fir_ols_os_kernel(const f2* __restrict__ x, const f2* __restrict__ hist, f2* __restrict__ new_hist,
                   const float4* __restrict__ Hs, const float4* __restrict__ tb, f2* __restrict__ y, long long n,
-                  long long lo, long long hi, long long q, long long nseg, int h2, int Lm1) {
+                  long long lo, long long hi, long long nseg, int h2, int Lm1) {
+    static_assert(EDGE && !HALO1 && !WIDE, "the interior segments take the short argument list");
     __shared__ __attribute__((aligned(16))) f2 img[16 * kRow];
-    long long seg;
-    if constexpr (EDGE) {
-        seg = (long long)blockIdx.x < lo ? (long long)blockIdx.x : hi + ((long long)blockIdx.x - lo);
-    } else {
-        const int xc = blockIdx.x & 7;
-        seg = lo + (long long)xc * q + (long long)(blockIdx.x >> 3);
-        const long long xe = lo + (long long)(xc + 1) * q;
-        if (seg >= (xe < hi ? xe : hi)) return;  // uniform over the workgroup
-    }
+    const long long seg = (long long)blockIdx.x < lo ? (long long)blockIdx.x : hi + ((long long)blockIdx.x - lo);
     const int V = 4096 - 256 * h2;
     const long long ch = blockIdx.y;
-    ols_os_segment<HALO1, WIDE, EDGE>(x + ch * n, hist + ch * Lm1,
-                                      (EDGE && new_hist != nullptr && seg == nseg - 1) ? new_hist + ch * Lm1 : nullptr,
-                                      Hs, tb, y + ch * n, seg * V - 256 * h2, n, Lm1, h2, img, threadIdx.x);
+    const long long base = seg * V - 256 * h2;
+    ols_os_segment<false, false, true>(x + ch * n + base, hist + ch * Lm1,
+                                       (new_hist != nullptr && seg == nseg - 1) ? new_hist + ch * Lm1 : nullptr, Hs, tb,
+                                       y + ch * n + base, base, n, Lm1, h2, img, threadIdx.x);
 }
 
 // every segment of every channel: the boundary segments (and the next history) in one small
@@ -301,6 +329,7 @@ hipError_t launch_fir_ols_os_t(const OlsPlan& p, const void* x, const void* hist
     if (h2 < 1 || h2 > 15 || Lm1 > 256 * h2 || (HALO1 && h2 != 1)) return hipErrorInvalidValue;
     const long long V = 4096 - 256 * h2;
     const long long nseg = ((long long)n + V - 1) / V;
+    if (nseg >= (1LL << 31)) return hipErrorInvalidValue;  // the interior kernel's segment numbers are 32-bit
     long long lo, hi;
     ols_interior_range((long long)n, h2, &lo, &hi);
     if (hi > nseg - 1) hi = nseg - 1;  // the last segment always runs in the boundary launch (history)
@@ -309,12 +338,12 @@ hipError_t launch_fir_ols_os_t(const OlsPlan& p, const void* x, const void* hist
     const long long q = (hi - lo + 7) / 8;
     hipLaunchKernelGGL((fir_ols_os_kernel<false, false, true>), dim3((unsigned)nedge, (unsigned)channels), dim3(256),
                        0, s, (const f2*)x, (const f2*)hist, (f2*)new_hist, (const float4*)p.d_pkt,
-                       (const float4*)p.d_ostab, (f2*)y, (long long)n, lo, hi, 0LL, nseg, h2, Lm1);
+                       (const float4*)p.d_ostab, (f2*)y, (long long)n, lo, hi, nseg, h2, Lm1);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || hi <= lo) return e;
     hipLaunchKernelGGL((fir_ols_os_kernel<HALO1, WIDE, false>), dim3((unsigned)(8 * q), (unsigned)channels), dim3(256),
-                       0, s, (const f2*)x, (const f2*)hist, (f2*)nullptr, (const float4*)p.d_pkt,
-                       (const float4*)p.d_ostab, (f2*)y, (long long)n, lo, hi, q, nseg, h2, Lm1);
+                       0, s, (const f2*)x, (f2*)y, (const float4*)p.d_pkt, (const float4*)p.d_ostab, (long long)n,
+                       (unsigned)lo, (unsigned)hi, (unsigned)q, h2);
     return hipGetLastError();
 }
 

@@ -27,6 +27,10 @@ $(foreach m,$(LAB_MAP),$(eval tools/_build/lab/$(word 1,$(subst :, ,$(m))).o: $(
 
 tools/_build/lab/iir_lab.o: HIPFLAGS += -fno-slp-vectorize
 tools/_build/lab/ols_lab.o: tools/lab/ols_os_lab_kernel.hip
+# as the product object (csrc/Makefile): the argument list preloaded into SGPRs (OLS_PRELOAD=0:
+# the lab kernels without it)
+OLS_PRELOAD ?= 16
+tools/_build/lab/ols_lab.o: HIPFLAGS += -mllvm -amdgpu-kernarg-preload-count=$(OLS_PRELOAD)
 
 $(OUT): $(patsubst %,tools/_build/lab/%.o,$(LAB_TUS)) $(PRODUCT_OBJS)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@.tmp $^ && mv -f $@.tmp $@

@@ -124,6 +124,20 @@ template <int ABL, int M> __device__ __forceinline__ void phase_mark() {
     hi = f2{h0, h1};
 }
 
+// lab clock stamp i of variant 262144 (SDSP_OLS_STAMPS builds only): s_memtime into st[i], pinned
+// in program order by scheduling barriers (which also keep the compiler from moving code across
+// the stamp: the perturbation is measured by running the stamped instance against variant 24)
+template <int ABL> __device__ __forceinline__ void ols_stamp([[maybe_unused]] unsigned long long* st, [[maybe_unused]] int i) {
+#ifdef SDSP_OLS_STAMPS
+    if constexpr ((ABL & 262144) != 0) {
+        __builtin_amdgcn_sched_barrier(0);
+        st[i] = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#endif
+}
+constexpr int kStampWords = 16;  // u64 per sampled workgroup: memtime, realtime at entry; the same at exit; stamps 4..8
+
 }  // namespace
 
 // ABL selects compile-time variants of the segment transform.  The product kernels
@@ -149,22 +163,34 @@ template <int ABL, int M> __device__ __forceinline__ void phase_mark() {
 // kernel's shape); 262144 clock stamps (lab builds that define SDSP_OLS_STAMPS only: every 32nd
 // workgroup records s_memtime / s_memrealtime at entry and exit into g_ols_stamps, a buffer no
 // other code reads; the in-kernel clock of MI355X_MICROARCH.md "DVFS give-back" item 6).
-template <int ABL, bool EDGE>
-__device__ __forceinline__ void ols_os_segment(const f2* __restrict__ x, const f2* __restrict__ hist,
+//
+// xw / yw point at the segment's window x[base, base + 4096) of its channel (the callers add the
+// segment's offset once, for both); base, n, hist, new_hist and Lm1 are read by EDGE only.  st: the
+// clock stamps of variant 262144 (SDSP_OLS_STAMPS builds), see ols_stamp.  ORD != 0 (lab): the
+// sixteen row loads and the two table loads issued exactly in a recorded order, a scheduling
+// barrier after each -- 1: the order the compiler gave round 6's product kernel (0, 4, 8, 12, CD,
+// 1, 5, 9, EF, 13, 3, 2, 6, 14, 15, 10, 7, 11), 2: the one it gives round 6's prologue in this
+// translation unit (CD, EF, 0, 1, 4, 8, 12, 9, 5, 13, 3, 2, 6, 14, 15, 10, 7, 11).
+template <int ABL, bool EDGE, int ORD = 0>
+__device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const f2* __restrict__ hist,
                                                f2* __restrict__ new_hist, const float4* __restrict__ Hs,
-                                               const float4* __restrict__ tb, f2* __restrict__ y, long long base,
+                                               const float4* __restrict__ tb, f2* __restrict__ yw, long long base,
                                                long long n, int Lm1, int h2, f2* img, int t, float4 (&tq)[6],
-                                               float4 (&hq)[8], bool first = true) {
+                                               float4 (&hq)[8], bool first = true,
+                                               unsigned long long* st = nullptr) {
     const int hi4 = t >> 4, lo4 = t & 15;
     if constexpr ((ABL & 16) != 0) h2 = 1;  // one halo row compiled in (the launcher checks h2 == 1)
     // the segment's window x[base, base + 4096) as a raw buffer.  EDGE (the boundary segments of a
     // call, launched apart so that the interior kernel carries no boundary code: its presence
     // alone cost the interior segments 1.9 %, profiles/r05/lab/r05e_olsburst.log): past the end of
     // the stream loads return 0 and stores are dropped, rows before it come from the history
-    const long long rem = n - base;
-    const int nrec = (!EDGE || rem >= 4096) ? 32768 : (int)(8 * rem);
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc((void*)(x + base), (short)0, nrec, kBufWord3);
-    const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)(y + base), (short)0, nrec, kBufWord3);
+    int nrec = 32768;
+    if constexpr (EDGE) {
+        const long long rem = n - base;
+        if (rem < 4096) nrec = (int)(8 * rem);
+    }
+    const auto rx = __builtin_amdgcn_make_buffer_rsrc((void*)xw, (short)0, nrec, kBufWord3);
+    const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)yw, (short)0, nrec, kBufWord3);
     const auto rt = __builtin_amdgcn_make_buffer_rsrc((void*)tb, (short)0, kOlsOsTabF4 * 16, kBufWord3);
     const auto rh = __builtin_amdgcn_make_buffer_rsrc((void*)Hs, (short)0,
                                                       (ABL & 268435456) ? 4 * kOlsHalfRow * 16 : 2048 * 16, kBufWord3);
@@ -218,12 +244,37 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ x, const f
             }
         }
     } else {
-        if constexpr ((ABL & 4194304) == 0) load_tables();
+        if constexpr ((ABL & 4194304) == 0 && (ORD == 0 || ORD >= 3)) load_tables();
         // the rows in row order (the compiler interleaves them as 0, 4, 1, 5, 8, 12, 9, 13, ...):
         // 2 % faster than the first radix-4 stage's order (0, 4, 8, 12, 1, 5, ...) and than either
         // order enforced with scheduling barriers (profiles/r05/lab/r05h_olsburst.log,
         // r05i_olsburst.log)
-        if constexpr ((ABL & 524288) != 0) {
+        if constexpr (ORD >= 3) {
+            // lab: the row loop written in another order, the compiler free to interleave it
+            constexpr int kSrc[3][16] = {{0, 1, 4, 8, 12, 9, 5, 13, 3, 2, 6, 14, 15, 10, 7, 11},
+                                         {0, 4, 8, 12, 1, 5, 9, 13, 3, 2, 6, 14, 15, 10, 7, 11},
+                                         {0, 4, 1, 5, 8, 12, 9, 13, 2, 6, 3, 7, 10, 14, 11, 15}};
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int r = kSrc[ORD - 3][i];
+                if ((ABL & 8) && (r == 0 || r == 15))
+                    v[r] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rx, 8 * t, 2048 * r, 0));
+                else v[r] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rx, 8 * t, 2048 * r, kLdAux));
+            }
+        } else if constexpr (ORD != 0) {
+            constexpr int kOrd[2][18] = {{0, 4, 8, 12, -1, 1, 5, 9, -2, 13, 3, 2, 6, 14, 15, 10, 7, 11},
+                                         {-1, -2, 0, 1, 4, 8, 12, 9, 5, 13, 3, 2, 6, 14, 15, 10, 7, 11}};
+#pragma unroll
+            for (int i = 0; i < 18; ++i) {
+                const int r = kOrd[ORD - 1][i];
+                if (r == -1) tq[0] = tab(t, 16 * kOlsOsTabCD);
+                else if (r == -2) tq[1] = tab(lo4, 16 * kOlsOsTabEF);
+                else if ((ABL & 8) && (r == 0 || r == 15))
+                    v[r] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rx, 8 * t, 2048 * r, 0));
+                else v[r] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rx, 8 * t, 2048 * r, kLdAux));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else if constexpr ((ABL & 524288) != 0) {
             // 16-byte lanes: lane t = 2c + h loads columns (2c, 2c + 1) of rows k + 8h, then one
             // DPP exchange per dword with its partner lane t ^ 1 gives it column t over the rows
             f4v q[8];
@@ -243,6 +294,7 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ x, const f
                     v[r] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rx, 8 * t, 2048 * r, 0));
                 else v[r] = __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rx, 8 * t, 2048 * r, kLdAux));
                 if constexpr ((ABL & 16777216) != 0) __builtin_amdgcn_sched_barrier(0);  // lab: issue in this order
+                if (i == 0) ols_stamp<ABL>(st, 4);  // the first row load is issued
             }
         }
         if constexpr ((ABL & 4194304) != 0) load_tables();  // lab: the tables after the rows
@@ -346,12 +398,22 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ x, const f
     if constexpr ((ABL & 1073741824) != 0) load_h();
 
     phase_mark<ABL, 0>();
+#ifdef SDSP_OLS_STAMPS
+    if constexpr ((ABL & 262144) != 0) {
+        // the rows have landed: every row is made a visible use here, so the stamp follows the wait
+        // for the last of them (the unstamped kernel starts its first butterflies a few rows earlier)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(v[r]));
+        ols_stamp<ABL>(st, 5);
+    }
+#endif
     // P1: DFT16 n2 -> k0, * W4096^(t k0) -> (k0, t)
     dft(v);
 #pragma unroll
     for (int k = 0; k < 16; ++k) col[k * kRow] = k == 0 ? v[0] : pmul(v[kout(k)], tw_pair(Cb, Da, k));
     if constexpr ((ABL & 536870912) != 0) load_h();
     __syncthreads();
+    ols_stamp<ABL>(st, 6);  // past the P1 -> P2 barrier
 
     phase_mark<ABL, 1>();
     // P2: lane (k0 = hi4, n0 = lo4): DFT16 n1 -> k1, * W256^(n0 k1) -> (k0, 16 k1 + n0)
@@ -374,6 +436,13 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ x, const f
 #pragma unroll
         for (int j = 0; j < 16; ++j) v[j] = r3[j];
         dft(v);
+#ifdef SDSP_OLS_STAMPS
+        if constexpr ((ABL & 262144) != 0) {  // the spectrum slice has arrived: the products start
+#pragma unroll
+            for (int p = 0; p < 8; ++p) asm volatile("" : "+v"(hq[p].x), "+v"(hq[p].y), "+v"(hq[p].z), "+v"(hq[p].w));
+            ols_stamp<ABL>(st, 7);
+        }
+#endif
         f2 u[16];
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
@@ -399,6 +468,7 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ x, const f
 #pragma unroll
     for (int k = 0; k < 16; ++k) r2[17 * k] = v[kout(k)];
     __syncthreads();
+    ols_stamp<ABL>(st, 8);  // past the P4 -> P5 barrier
 
     phase_mark<ABL, 4>();
     // P5: lane t: * conj W4096^(t k0), IDFT16 k0 -> n2; row n2 at v[kout(n2)].  The bases are
@@ -438,19 +508,82 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ x, const f
 }
 
 #ifdef SDSP_OLS_STAMPS
-__device__ unsigned long long g_ols_stamps[4 * 8192];
+__device__ unsigned long long g_ols_stamps[kStampWords * 8192];
 #endif
+
+// the stamps of one workgroup (variant 262144): entry (memtime, realtime) at the kernel's first
+// instruction, ...
+template <int ABL> __device__ __forceinline__ void ols_stamps_begin([[maybe_unused]] unsigned long long* st) {
+#ifdef SDSP_OLS_STAMPS
+    if constexpr ((ABL & 262144) != 0) {
+        st[0] = __builtin_amdgcn_s_memtime(), st[1] = __builtin_amdgcn_s_memrealtime();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#endif
+}
+// ... and exit (the last store is issued); wave 0 of every 32nd workgroup writes them, with vector
+// stores, into a buffer no other code reads
+template <int ABL> __device__ __forceinline__ void ols_stamps_end([[maybe_unused]] unsigned long long* st) {
+#ifdef SDSP_OLS_STAMPS
+    if constexpr ((ABL & 262144) != 0) {
+        __builtin_amdgcn_sched_barrier(0);
+        st[2] = __builtin_amdgcn_s_memtime(), st[3] = __builtin_amdgcn_s_memrealtime();
+        if (threadIdx.x == 0 && (blockIdx.x & 31) == 0) {
+            unsigned long long* o = g_ols_stamps + kStampWords * ((blockIdx.x >> 5) & 8191);
+#pragma unroll
+            for (int i = 0; i < 9; ++i) o[i] = st[i];
+        }
+    }
+#endif
+}
+
+// variants that need the long argument list below: the boundary segments inside the interior
+// launch and the two-segment form
+constexpr bool ols_long_list_only(int abl) { return (abl & (33554432 | 134217728)) != 0; }
+// variants also instantiated with the long list's prologue (round 6's, for A/B against the short
+// list's: the third field of an ols_lab.py case)
+constexpr bool ols_round6_prologue(int abl) {
+    return ols_long_list_only(abl) || abl == 24 || abl == 262168 || abl == 4194328;
+}
 
 // Interior segments [lo, hi) of every channel (whole window inside the stream): workgroup b
 // runs on XCD b % 8 and takes segment lo + (b % 8) q + b / 8, so each XCD streams one contiguous
-// eighth of the call in order.  EDGE: the boundary segments [0, lo) and [hi, nseg) (block b takes
-// segment b < lo ? b : hi + b - lo), the last one writing the next history (new_hist).
+// eighth of the call in order.  The short argument list and the 32-bit scalar prologue of the
+// product (kern_fir_ols_os.hip): the grid is 8 q wide, so only seg >= hi is refused.
+template <int ABL, int ORD>
+__global__ void __launch_bounds__(256, 4)
+fir_ols_os_short_kernel(const f2* __restrict__ x, f2* __restrict__ y, const float4* __restrict__ Hs,
+                  const float4* __restrict__ tb, long long stride, unsigned lo, unsigned hi, unsigned q, int h2) {
+    static_assert(!ols_long_list_only(ABL));
+    __shared__ __attribute__((aligned(16))) f2 img[16 * kRow];
+    unsigned long long st[9] = {};
+    ols_stamps_begin<ABL>(st);
+    unsigned j = blockIdx.x >> 3;
+    if constexpr ((ABL & 1024) != 0) j = j < (q + 1) / 2 ? 2 * j : 2 * (j - (q + 1) / 2) + 1;
+    const unsigned seg = lo + (blockIdx.x & 7u) * q + j;
+    if (seg >= hi) return;  // uniform over the workgroup
+    if constexpr ((ABL & 16) != 0) h2 = 1;
+    // window start in samples: seg V - 256 h2 >= 0 (lo >= 1), one 32 x 32 -> 64 multiply
+    const unsigned H = 256u * (unsigned)h2;
+    const long long off = (long long)((unsigned long long)seg * (4096u - H)) - (long long)H +
+                          (long long)blockIdx.y * stride;
+    float4 tq[6], hq[8];
+    ols_os_segment<ABL, false, ORD>(x + off, nullptr, nullptr, Hs, tb, y + off, 0, 0, 0, h2, img, threadIdx.x, tq, hq,
+                                    true, st);
+    ols_stamps_end<ABL>(st);
+}
+
+// The long argument list: the boundary segments [0, lo) and [hi, nseg) (EDGE: block b takes
+// segment b < lo ? b : hi + b - lo, the last one writing the next history, new_hist), and the
+// interior segments with round 6's prologue (64-bit segment arithmetic after an argument fetch).
 template <int ABL, bool EDGE>
 __global__ void __launch_bounds__(256, 4)
 fir_ols_os_kernel(const f2* __restrict__ x, const f2* __restrict__ hist, f2* __restrict__ new_hist,
                   const float4* __restrict__ Hs, const float4* __restrict__ tb, f2* __restrict__ y, long long n,
                   long long lo, long long hi, long long q, long long nseg, int h2, int Lm1) {
     __shared__ __attribute__((aligned(16))) f2 img[16 * kRow];
+    unsigned long long st[9] = {};
+    ols_stamps_begin<ABL>(st);
     long long seg;
     if constexpr (!EDGE && (ABL & 33554432) != 0) {
         // lab: the boundary segments as extra workgroups past the interior grid, on their own
@@ -460,11 +593,11 @@ fir_ols_os_kernel(const f2* __restrict__ x, const f2* __restrict__ hist, f2* __r
             const long long b = (long long)blockIdx.x - nb;
             const long long sg = b < lo ? b : hi + (b - lo);
             const long long c = blockIdx.y;
+            const long long bs = sg * (4096 - 256 * h2) - 256 * h2;
             float4 tq[6], hq[8];
-            ols_os_segment<0, true>(x + c * n, hist + c * Lm1,
+            ols_os_segment<0, true>(x + c * n + bs, hist + c * Lm1,
                                     (new_hist != nullptr && sg == nseg - 1) ? new_hist + c * Lm1 : nullptr, Hs, tb,
-                                    y + c * n, sg * (4096 - 256 * h2) - 256 * h2, n, Lm1, h2, img, threadIdx.x, tq,
-                                    hq);
+                                    y + c * n + bs, bs, n, Lm1, h2, img, threadIdx.x, tq, hq);
             return;
         }
     }
@@ -486,8 +619,9 @@ fir_ols_os_kernel(const f2* __restrict__ x, const f2* __restrict__ hist, f2* __r
             const long long sg = s0 + k * qh;
             if (sg >= xe) return;    // uniform over the workgroup
             if (k) __syncthreads();  // the first segment's P5 reads are done before P1 rewrites the image
-            ols_os_segment<ABL, false>(x + ch * n, hist + ch * Lm1, nullptr, Hs, tb, y + ch * n,
-                                       sg * V - 256 * h2, n, Lm1, h2, img, threadIdx.x, tq, hq, k == 0);
+            const long long bs = sg * V - 256 * h2;
+            ols_os_segment<ABL, false>(x + ch * n + bs, hist + ch * Lm1, nullptr, Hs, tb, y + ch * n + bs, bs, n, Lm1,
+                                       h2, img, threadIdx.x, tq, hq, k == 0);
         }
         return;
     }
@@ -501,35 +635,28 @@ fir_ols_os_kernel(const f2* __restrict__ x, const f2* __restrict__ hist, f2* __r
         const long long xe = lo + (long long)(xc + 1) * q;
         if (seg >= (xe < hi ? xe : hi)) return;  // uniform over the workgroup
     }
-#ifdef SDSP_OLS_STAMPS
-    unsigned long long m0 = 0, r0 = 0;
-    if constexpr ((ABL & 262144) != 0) m0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    ols_os_segment<ABL, EDGE>(x + ch * n, hist + ch * Lm1,
+    const long long base = seg * V - 256 * h2;
+    ols_os_segment<ABL, EDGE>(x + ch * n + base, hist + ch * Lm1,
                               (EDGE && new_hist != nullptr && seg == nseg - 1) ? new_hist + ch * Lm1 : nullptr, Hs,
-                              tb, y + ch * n, seg * V - 256 * h2, n, Lm1, h2, img, threadIdx.x, tq, hq);
-#ifdef SDSP_OLS_STAMPS
-    if constexpr ((ABL & 262144) != 0) {
-        const unsigned long long m1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        if (threadIdx.x == 0 && (blockIdx.x & 31) == 0) {
-            unsigned long long* o = g_ols_stamps + 4 * ((blockIdx.x >> 5) & 8191);
-            o[0] = m0, o[1] = r0, o[2] = m1, o[3] = r1;
-        }
-    }
-#endif
+                              tb, y + ch * n + base, base, n, Lm1, h2, img, threadIdx.x, tq, hq, true, st);
+    ols_stamps_end<ABL>(st);
 }
 
 // every segment of every channel: the boundary segments (and the next history) in one small
 // launch, the interior ones in the XCD-ordered grid; ABL as above for the interior kernel (0 = the
-// product kernel)
+// product kernel).  prologue 2: the interior launch through the long list's prologue, where the
+// variant is built with it (ols_round6_prologue), for A/B against the product's; 3, 4 (variant 24):
+// the product's prologue with the loads pinned in order 1, 2 (ORD of ols_os_segment).
 template <int ABL>
 hipError_t launch_fir_ols_os_t(const OlsPlan& p, const void* x, const void* hist, void* new_hist, void* y, size_t n,
-                               int Lm1, size_t channels, hipStream_t s, size_t dyn_lds) {
+                               int Lm1, size_t channels, hipStream_t s, size_t dyn_lds, int prologue = 1) {
+    const bool round6 = prologue == 2;
     if (n == 0) return hipSuccess;
     const int h2 = p.halo_rows;
     if (h2 < 1 || h2 > 15 || Lm1 > 256 * h2) return hipErrorInvalidValue;
     const long long V = 4096 - 256 * h2;
     const long long nseg = ((long long)n + V - 1) / V;
+    if (nseg >= (1LL << 31)) return hipErrorInvalidValue;  // the short list's segment numbers are 32-bit
     long long lo, hi;
     ols_interior_range((long long)n, h2, &lo, &hi);
     if (hi > nseg - 1) hi = nseg - 1;  // the last segment always runs in the boundary launch (history)
@@ -550,9 +677,27 @@ hipError_t launch_fir_ols_os_t(const OlsPlan& p, const void* x, const void* hist
     if (e != hipSuccess || hi <= lo) return e;
     // the interior kernel's spectrum table: the half table for real taps (ABL 268435456)
     const float4* hs = (const float4*)((ABL & 268435456) ? p.d_hhalf : p.d_pkt);
-    hipLaunchKernelGGL((fir_ols_os_kernel<ABL, false>), dim3((unsigned)(8 * qg), (unsigned)channels), dim3(256), dyn_lds,
-                       s, (const f2*)x, (const f2*)hist, (f2*)nullptr, hs, (const float4*)p.d_ostab,
-                       (f2*)y, (long long)n, lo, hi, q, nseg, h2, Lm1);
+    if constexpr (ols_round6_prologue(ABL)) {
+        if (round6 || ols_long_list_only(ABL)) {
+            hipLaunchKernelGGL((fir_ols_os_kernel<ABL, false>), dim3((unsigned)(8 * qg), (unsigned)channels), dim3(256),
+                               dyn_lds, s, (const f2*)x, (const f2*)hist, (f2*)nullptr, hs, (const float4*)p.d_ostab,
+                               (f2*)y, (long long)n, lo, hi, q, nseg, h2, Lm1);
+            return hipGetLastError();
+        }
+    }
+    if constexpr (!ols_long_list_only(ABL)) {
+        const dim3 grid((unsigned)(8 * q), (unsigned)channels);
+#define SDSP_OLS_SHORT(ORD)                                                                                         \
+    hipLaunchKernelGGL((fir_ols_os_short_kernel<ABL, ORD>), grid, dim3(256), dyn_lds, s, (const f2*)x, (f2*)y, hs, \
+                       (const float4*)p.d_ostab, (long long)n, (unsigned)lo, (unsigned)hi, (unsigned)q, h2)
+        if (ABL == 24 && prologue == 3) SDSP_OLS_SHORT(ABL == 24 ? 1 : 0);
+        else if (ABL == 24 && prologue == 4) SDSP_OLS_SHORT(ABL == 24 ? 2 : 0);
+        else if (ABL == 24 && prologue == 5) SDSP_OLS_SHORT(ABL == 24 ? 3 : 0);
+        else if (ABL == 24 && prologue == 6) SDSP_OLS_SHORT(ABL == 24 ? 4 : 0);
+        else if (ABL == 24 && prologue == 7) SDSP_OLS_SHORT(ABL == 24 ? 5 : 0);
+        else SDSP_OLS_SHORT(0);
+#undef SDSP_OLS_SHORT
+    }
     return hipGetLastError();
 }
 

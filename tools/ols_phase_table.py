@@ -87,8 +87,9 @@ def table(phases):
 
 def main():
     obj = sys.argv[1]
-    marked = ops(disasm(obj, r"fir_ols_os_kernelILi88ELb0"))
-    prod = ops(disasm(obj, r"fir_ols_os_kernelILi24ELb0"))
+    # the short-list (product prologue) instances, loads in the compiler's order
+    marked = ops(disasm(obj, r"fir_ols_os_short_kernelILi88ELi0"))
+    prod = ops(disasm(obj, r"fir_ols_os_short_kernelILi24ELi0"))
     phases = split(marked)
     assert len(phases) == 6, len(phases)
     rows = table(phases)
