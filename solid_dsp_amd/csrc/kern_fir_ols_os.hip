@@ -22,14 +22,17 @@
 //    positions (k0, 16 j + n0), in P3 lane (k0, k1) owns (k0, 16 k1 + j), in
 //    P1/P5 lane t owns column t -- each lane reads and rewrites only its own
 //    positions inside a phase, so one region suffices.  P2, P3 and P4 of wave w
-//    touch only rows k0 = 4w .. 4w + 3, so only P1 -> P2 and P4 -> P5 need a
-//    workgroup barrier;
+//    touch only four rows of its own (k0 = 4w .. 4w + 3; with a real g the rows
+//    of ols_rg_row, 122 VGPRs), so only P1 -> P2 and P4 -> P5 need a workgroup
+//    barrier;
 //  * lane t owns column t in P1 / P5: 8-byte buffer loads and stores per row
 //    (row offsets in SGPRs, no address arithmetic in VGPRs);
 //  * no twiddle tables in LDS or per-lane tables in registers: W4096^(t k) =
 //    D_{k>>2} C_{k&3} and W256^(l k) = F_{k>>2} E_{k&3} from per-lane bases
 //    (C1, D1, E1, F1: two float4 from L2; C2 = C1 C1, C3 = C2 C1, ...), the
-//    spectrum slice of P3 loaded from L2 in P2;
+//    spectrum slice of P3 loaded from L2 in P2 (eight 16-byte loads per lane;
+//    four when g is real, the other half read from the mirror lane's registers
+//    through DPP: the REALG instances below);
 //  * nontemporal input loads and stores (the stream is read and written once).
 //
 // LDS image: element (r, c) at r * 272 + c + (c >> 4) (one 8-byte pad per
@@ -102,6 +105,98 @@ __device__ __forceinline__ void pair_exchange(f2 a, f2 b, f2& lo, f2& hi) {
     hi = f2{h0, h1};
 }
 
+// ---- real circular kernel g (real taps, real scale): H[N - k] = conj H[k] ----
+//
+// Bin (k0, k1, k2) = k0 + 16 k1 + 256 k2 mirrors (16 - k0, 15 - k1, 15 - k2) for k0 >= 1, so the
+// bins k2 >= 8 of lane (k0, k1) are the conjugates of the bins k2' = 15 - k2 < 8 of lane
+// (16 - k0, 15 - k1).  The REALG instances deal the P2 - P4 rows to the lanes so that this mirror
+// lane is the lane at the mirrored position of the same 16-lane DPP row: with g = (t >> 4) & 3 and
+// j = t & 15, wave w < 3 holds the row pairs (2w + 1, 15 - 2w) in its groups g = 0, 1 and
+// (2w + 2, 14 - 2w) in g = 2, 3; in the first group of a pair (a, 16 - a) lanes j < 8 take row a and
+// lanes j >= 8 row 16 - a, in the second the reverse.  Wave 3 holds rows 0 and 8 whole (g = 0, 1;
+// row 8 mirrors within itself, row 0 is the exception below) and the pair (7, 9).  The index
+// within the row stays j, a wave still owns four rows, and the rows of a pair lie an even number
+// of rows (a multiple of 2 * 544 dwords) apart, so the LDS bank pattern is the plain layout's.
+constexpr int ols_rg_row(int t) {
+    const int w = t >> 6, g = (t >> 4) & 3, j = t & 15;
+    if (w == 3 && g < 2) return 8 * g;
+    const int a = w == 3 ? 7 : 2 * w + 1 + (g >> 1);
+    return (g & 1) != (j >> 3) ? 16 - a : a;
+}
+// the same map for the kernel, without a branch: the rows of the two halves (j < 8, j >= 8) of the
+// sixteen 16-lane groups, four bits each, in two 64-bit constants
+constexpr unsigned long long ols_rg_pack(int half) {
+    unsigned long long v = 0;
+    for (int grp = 0; grp < 16; ++grp) v |= (unsigned long long)ols_rg_row(16 * grp + 8 * half) << (4 * grp);
+    return v;
+}
+constexpr int ols_rg_row_packed(int t) {
+    return (int)(((t & 8) ? ols_rg_pack(1) : ols_rg_pack(0)) >> (4 * (t >> 4))) & 15;
+}
+constexpr bool ols_rg_packed_is_the_map() {
+    for (int t = 0; t < 256; ++t)
+        if (ols_rg_row_packed(t) != ols_rg_row(t)) return false;
+    return true;
+}
+static_assert(ols_rg_packed_is_the_map(), "the packed form is ols_rg_row");
+constexpr bool ols_rg_bijective() {
+    bool seen[256] = {};
+    for (int t = 0; t < 256; ++t) {
+        const int r = ols_rg_row(t);
+        if (r < 0 || r > 15 || seen[16 * r + (t & 15)]) return false;
+        seen[16 * r + (t & 15)] = true;
+    }
+    return true;
+}
+constexpr bool ols_rg_four_rows_per_wave() {
+    for (int w = 0; w < 4; ++w) {
+        int rows = 0, count = 0;
+        for (int l = 0; l < 64; ++l) rows |= 1 << ols_rg_row(64 * w + l);
+        for (int r = 0; r < 16; ++r) count += (rows >> r) & 1;
+        if (count != 4) return false;
+    }
+    return true;
+}
+constexpr bool ols_rg_mirror_in_dpp_row() {
+    for (int t = 0; t < 256; ++t) {
+        const int r = ols_rg_row(t), m = (t & ~15) | (15 - (t & 15));  // row_mirror's source lane
+        if (r != 0 && (ols_rg_row(m) != 16 - r || (m & 15) != 15 - (t & 15))) return false;
+    }
+    return true;
+}
+static_assert(ols_rg_bijective(), "the lane map covers 16 rows x 16 indices once");
+static_assert(ols_rg_four_rows_per_wave(), "P2 - P4 of a wave touch four rows (wave-level hand-offs)");
+static_assert(ols_rg_mirror_in_dpp_row(), "row != 0: position 15 - j of the group holds (16 - row, 15 - k1)");
+
+// a * conj(b) with the operations of pmul(a, {b.x, -b.y}), bit for bit: what the boundary
+// instance computes from the full table, whose entry is that conjugate
+__device__ __forceinline__ f2 pmul_cj(f2 a, f2 b) {
+    f2 t, r;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0]" : "=v"(t) : "v"(a), "v"(b));
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] neg_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(b), "v"(t));
+    return r;
+}
+
+// The two bins of one k-pair whose spectrum values are the conjugates of the MIRROR lane's pair m
+// (halves swapped): r0 = a0 * conj(m.zw), r1 = a1 * conj(m.xy), m read from the lane at the
+// mirrored position of the 16-lane row: four v_mov_b32 with a row_mirror DPP operand, then the
+// packed products.  (The lab's other form, the products themselves as v_mul / v_fmac with the DPP
+// operand and no copy, measured 1.4 % slower: profiles/r08/LAB.md.)  Every lane of the wave must
+// be active (a DPP read of an inactive lane writes nothing); the s_nop covers the DPP
+// read-after-VALU-write hazard should the compiler have moved m just before.
+__device__ __forceinline__ void mirror_products(f2 a0, f2 a1, float4 m, f2& r0, f2& r1) {
+    float bx, by, cx, cy;
+    asm("s_nop 1\n\t"
+        "v_mov_b32_dpp %0, %4 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_mov_b32_dpp %1, %5 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_mov_b32_dpp %2, %6 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_mov_b32_dpp %3, %7 row_mirror row_mask:0xf bank_mask:0xf"
+        : "=&v"(bx), "=&v"(by), "=&v"(cx), "=&v"(cy)
+        : "v"(m.z), "v"(m.w), "v"(m.x), "v"(m.y));
+    r0 = pmul_cj(a0, f2{bx, by});
+    r1 = pmul_cj(a1, f2{cx, cy});
+}
+
 }  // namespace
 
 // One segment of the transform.  Template parameters (the product's instances only):
@@ -114,16 +209,24 @@ __device__ __forceinline__ void pair_exchange(f2 a, f2 b, f2& lo, f2& hi) {
 //          more than the wider accesses save);
 //   EDGE   the boundary segments of a call (launched apart, so the interior kernel carries no
 //          boundary code): past the end of the stream loads return 0 and stores are dropped, rows
-//          before it come from the history, and the call's last segment writes the next history.
+//          before it come from the history, and the call's last segment writes the next history;
+//   REALG  g is real (OlsPlan::d_hhalf): Hs is the half table, float4 [4][kOlsHalfRow], the rows of
+//          P2 - P4 are dealt by ols_rg_row, every lane loads the four k-pairs k2 < 8 of its own
+//          (row, k1) and multiplies the bins k2 >= 8 by the conjugates of its mirror lane's, read
+//          through DPP (mirror_products): four 16-byte spectrum loads per lane instead of eight.  The 16
+//          lanes of row 0, whose mirror (0, 16 - k1) is no DPP partner, load their mirror's four
+//          pairs as well (wave 3 only).  Same bits as the full-table form on a table with
+//          H[N - k] = conj H[k] exactly (runtime.cpp ols_build makes it so).
 //
 // xw / yw point at the segment's window x[base, base + 4096) of its channel (the callers add the
 // segment's offset once, for both); base, n, hist, new_hist and Lm1 are read by EDGE only.
-template <bool HALO1, bool WIDE, bool EDGE>
+template <bool HALO1, bool WIDE, bool EDGE, bool REALG>
 __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const f2* __restrict__ hist,
                                                f2* __restrict__ new_hist, const float4* __restrict__ Hs,
                                                const float4* __restrict__ tb, f2* __restrict__ yw, long long base,
                                                long long n, int Lm1, int h2, f2* img, int t) {
-    const int hi4 = t >> 4, lo4 = t & 15;
+    static_assert(!(EDGE && REALG), "the boundary segments read the full table");
+    const int lo4 = t & 15;
     if constexpr (HALO1) h2 = 1;  // compiled in (the launcher checks h2 == 1)
     // the segment's window as a raw buffer
     int nrec = 32768;
@@ -134,7 +237,7 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
     const auto rx = __builtin_amdgcn_make_buffer_rsrc((void*)xw, (short)0, nrec, kBufWord3);
     const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)yw, (short)0, nrec, kBufWord3);
     const auto rt = __builtin_amdgcn_make_buffer_rsrc((void*)tb, (short)0, kOlsOsTabF4 * 16, kBufWord3);
-    const auto rh = __builtin_amdgcn_make_buffer_rsrc((void*)Hs, (short)0, 2048 * 16, kBufWord3);
+    const auto rh = __builtin_amdgcn_make_buffer_rsrc((void*)Hs, (short)0, (REALG ? 4 * kOlsHalfRow : 2048) * 16, kBufWord3);
     // twiddle bases: {C1, D1} of column t and {E1, F1} of row lo4 (runtime.cpp ols_build), requested
     // before the segment's rows (L2 hits that land while the rows stream in)
     const float4 cd = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rt, 16 * t, 16 * kOlsOsTabCD, 0));
@@ -200,6 +303,7 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
         Fa[0] = f1, Fa[1] = f2_, Fa[2] = pmul(f2_, f1);
     }
     f2* col = img + t + (t >> 4);  // (r, t) at col[r * kRow]
+    const int hi4 = REALG ? ols_rg_row_packed(t) : t >> 4;  // the lane's row in P2 - P4
 
     // P1: DFT16 n2 -> k0, * W4096^(t k0) -> (k0, t)
     pdft16f<false>(v);
@@ -211,9 +315,23 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
     f2* r2 = img + hi4 * kRow + lo4;  // (hi4, 16 j + lo4) at r2[17 j]
 #pragma unroll
     for (int j = 0; j < 16; ++j) v[j] = r2[17 * j];
-    float4 hq[8];  // the spectrum slice of lane (k0, k1) = t for P3, k-pair major
+    float4 hq[8];  // the spectrum slice of lane (k0, k1) for P3, k-pair major
+    if constexpr (REALG) {
+        // pairs p < 4 of this lane; row 0 alone also pair 7 - p of its mirror (0, 16 - k1) into
+        // hq[p], p >= 4 (k1 = 0: the table's tail entry) -- the other lanes never read theirs
 #pragma unroll
-    for (int p = 0; p < 8; ++p) hq[p] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rh, 16 * t, 4096 * p, 0));
+        for (int p = 0; p < 4; ++p)
+            hq[p] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rh, 16 * (16 * hi4 + lo4), 16 * kOlsHalfRow * p, 0));
+        if (hi4 == 0) {
+            const int ml = lo4 ? 16 - lo4 : 256;
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                hq[7 - p] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rh, 16 * ml, 16 * kOlsHalfRow * p, 0));
+        }
+    } else {
+#pragma unroll
+        for (int p = 0; p < 8; ++p) hq[p] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rh, 16 * t, 4096 * p, 0));
+    }
     f2 w2[16];  // W256^(lo4 k), used by P2 (n0 = lo4) and P3 (k1 = lo4)
 #pragma unroll
     for (int k = 1; k < 16; ++k) w2[k] = tw_pair(Eb, Fa, k);
@@ -230,9 +348,22 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
         pdft16f<false>(v);
         f2 u[16];
 #pragma unroll
-        for (int p = 0; p < 8; ++p) {
+        for (int p = 0; p < (REALG ? 4 : 8); ++p) {
             u[2 * p] = pmul(v[kout(2 * p)], f2{hq[p].x, hq[p].y});
             u[2 * p + 1] = pmul(v[kout(2 * p + 1)], f2{hq[p].z, hq[p].w});
+        }
+        if constexpr (REALG) {
+            // bins k2 = 2p, 2p + 1 >= 8: conj of bins 15 - 2p, 14 - 2p (pair 7 - p, halves swapped) of
+            // the mirror lane; all lanes first (DPP needs the whole wave), then row 0 over its own
+#pragma unroll
+            for (int p = 4; p < 8; ++p) mirror_products(v[kout(2 * p)], v[kout(2 * p + 1)], hq[7 - p], u[2 * p], u[2 * p + 1]);
+            if (hi4 == 0) {
+#pragma unroll
+                for (int p = 4; p < 8; ++p) {
+                    u[2 * p] = pmul_cj(v[kout(2 * p)], f2{hq[p].z, hq[p].w});
+                    u[2 * p + 1] = pmul_cj(v[kout(2 * p + 1)], f2{hq[p].x, hq[p].y});
+                }
+            }
         }
         pdft16f<true>(u);
 #pragma unroll
@@ -284,7 +415,7 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
 // the compiler's fallback), and segment arithmetic in 32 bits on the scalar unit (the launcher
 // refuses 2^31 or more segments): no scalar-memory wait and no vector compare before the loads.
 // stride is the distance between channels in samples.
-template <bool HALO1, bool WIDE, bool EDGE>
+template <bool HALO1, bool WIDE, bool EDGE, bool REALG>
 __global__ void __launch_bounds__(256, 4)
 fir_ols_os_kernel(const f2* __restrict__ x, f2* __restrict__ y, const float4* __restrict__ Hs,
                   const float4* __restrict__ tb, long long stride, unsigned lo, unsigned hi, unsigned q, int h2) {
@@ -297,7 +428,7 @@ fir_ols_os_kernel(const f2* __restrict__ x, f2* __restrict__ y, const float4* __
     const unsigned H = 256u * (unsigned)h2;
     const long long off = (long long)((unsigned long long)seg * (4096u - H)) - (long long)H +
                           (long long)blockIdx.y * stride;
-    ols_os_segment<HALO1, WIDE, false>(x + off, nullptr, nullptr, Hs, tb, y + off, 0, 0, 0, h2, img, threadIdx.x);
+    ols_os_segment<HALO1, WIDE, false, REALG>(x + off, nullptr, nullptr, Hs, tb, y + off, 0, 0, 0, h2, img, threadIdx.x);
 }
 
 // The boundary segments [0, lo) and [hi, nseg) of every channel (block b takes segment
@@ -314,14 +445,14 @@ fir_ols_os_kernel(const f2* __restrict__ x, const f2* __restrict__ hist, f2* __r
     const int V = 4096 - 256 * h2;
     const long long ch = blockIdx.y;
     const long long base = seg * V - 256 * h2;
-    ols_os_segment<false, false, true>(x + ch * n + base, hist + ch * Lm1,
+    ols_os_segment<false, false, true, false>(x + ch * n + base, hist + ch * Lm1,
                                        (new_hist != nullptr && seg == nseg - 1) ? new_hist + ch * Lm1 : nullptr, Hs, tb,
                                        y + ch * n + base, base, n, Lm1, h2, img, threadIdx.x);
 }
 
 // every segment of every channel: the boundary segments (and the next history) in one small
-// launch, the interior ones in the XCD-ordered grid
-template <bool HALO1, bool WIDE>
+// launch from the full table, the interior ones in the XCD-ordered grid (REALG: from the half table)
+template <bool HALO1, bool WIDE, bool REALG>
 hipError_t launch_fir_ols_os_t(const OlsPlan& p, const void* x, const void* hist, void* new_hist, void* y, size_t n,
                                int Lm1, size_t channels, hipStream_t s) {
     if (n == 0) return hipSuccess;
@@ -341,17 +472,22 @@ hipError_t launch_fir_ols_os_t(const OlsPlan& p, const void* x, const void* hist
                        (const float4*)p.d_ostab, (f2*)y, (long long)n, lo, hi, nseg, h2, Lm1);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || hi <= lo) return e;
-    hipLaunchKernelGGL((fir_ols_os_kernel<HALO1, WIDE, false>), dim3((unsigned)(8 * q), (unsigned)channels), dim3(256),
-                       0, s, (const f2*)x, (f2*)y, (const float4*)p.d_pkt, (const float4*)p.d_ostab, (long long)n,
+    hipLaunchKernelGGL((fir_ols_os_kernel<HALO1, WIDE, false, REALG>), dim3((unsigned)(8 * q), (unsigned)channels), dim3(256),
+                       0, s, (const f2*)x, (f2*)y, (const float4*)(REALG ? p.d_hhalf : p.d_pkt), (const float4*)p.d_ostab, (long long)n,
                        (unsigned)lo, (unsigned)hi, (unsigned)q, h2);
     return hipGetLastError();
 }
 
 hipError_t launch_fir_ols_os(const OlsPlan& p, const void* x, const void* hist, void* new_hist, void* y, size_t n,
                              int Lm1, size_t channels, hipStream_t s, bool wide) {
-    if (wide) return launch_fir_ols_os_t<false, true>(p, x, hist, new_hist, y, n, Lm1, channels, s);
-    if (p.halo_rows == 1) return launch_fir_ols_os_t<true, false>(p, x, hist, new_hist, y, n, Lm1, channels, s);
-    return launch_fir_ols_os_t<false, false>(p, x, hist, new_hist, y, n, Lm1, channels, s);
+    if (p.d_hhalf != nullptr) {  // g is real: the half-spectrum interior instances
+        if (wide) return launch_fir_ols_os_t<false, true, true>(p, x, hist, new_hist, y, n, Lm1, channels, s);
+        if (p.halo_rows == 1) return launch_fir_ols_os_t<true, false, true>(p, x, hist, new_hist, y, n, Lm1, channels, s);
+        return launch_fir_ols_os_t<false, false, true>(p, x, hist, new_hist, y, n, Lm1, channels, s);
+    }
+    if (wide) return launch_fir_ols_os_t<false, true, false>(p, x, hist, new_hist, y, n, Lm1, channels, s);
+    if (p.halo_rows == 1) return launch_fir_ols_os_t<true, false, false>(p, x, hist, new_hist, y, n, Lm1, channels, s);
+    return launch_fir_ols_os_t<false, false, false>(p, x, hist, new_hist, y, n, Lm1, channels, s);
 }
 
 }  // namespace sdsp

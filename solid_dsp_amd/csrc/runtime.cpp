@@ -192,6 +192,16 @@ int ols_build(sdsp_fir* h) {
         }
         G[k] = {re / N, im / N};
     }
+    // real taps, real scale, complex samples: g is real, so its spectrum is conjugate-symmetric.
+    // The sums above are so only to rounding; the symmetry is made exact here, before anything is
+    // rounded to f32 or packed, so that the full tables and the half table hold the same values
+    // and every kernel computes the same bits from either (kern_fir_ols_os.hip REALG)
+    const bool real_taps = !coef_is_complex(h->dtype) && !ols_real(h) && s.im == 0.0;
+    if (real_taps) {
+        for (int k = 1; k < N / 2; ++k) G[N - k] = cd{G[k].re, -G[k].im};
+        G[0].im = 0.0;
+        G[N / 2].im = 0.0;
+    }
     std::vector<float> Hs(2 * 4096), tw1(2 * 4096), tw2(2 * 256);
     for (int t = 0; t < 256; ++t) {
         const int k0 = t >> 4, k1 = t & 15;
@@ -282,7 +292,6 @@ int ols_build(sdsp_fir* h) {
     // float4 [p][i] = {H(i, 2p), H(i, 2p + 1)} for p < 4, H(i, k2) = G[k0 + 16 k1 + 256 k2] of
     // lane i = 16 k0 + k1; entry i = 256 is the mirror of lane (0, 0), whose bins k2 >= 8 mirror
     // k2' = 16 - k2 (k2' = 8 included): stored so that the kernel's conj-and-swap yields them
-    const bool real_taps = !coef_is_complex(h->dtype) && !real;  // (the lab's c32 kernels only)
     if (real_taps) {
         std::vector<float> hh(4 * 4 * kOlsHalfRow);
         auto set = [&](int q, int i, int half, cd v) {

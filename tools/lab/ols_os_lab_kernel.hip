@@ -124,6 +124,119 @@ template <int ABL, int M> __device__ __forceinline__ void phase_mark() {
     hi = f2{h0, h1};
 }
 
+// ---- real circular kernel g (real taps, real scale): H[N - k] = conj H[k] ----
+//
+// Bin (k0, k1, k2) = k0 + 16 k1 + 256 k2 mirrors (16 - k0, 15 - k1, 15 - k2) for k0 >= 1, so the
+// bins k2 >= 8 of lane (k0, k1) are the conjugates of the bins k2' = 15 - k2 < 8 of lane
+// (16 - k0, 15 - k1).  The REALG instances deal the P2 - P4 rows to the lanes so that this mirror
+// lane is the lane at the mirrored position of the same 16-lane DPP row: with g = (t >> 4) & 3 and
+// j = t & 15, wave w < 3 holds the row pairs (2w + 1, 15 - 2w) in its groups g = 0, 1 and
+// (2w + 2, 14 - 2w) in g = 2, 3; in the first group of a pair (a, 16 - a) lanes j < 8 take row a and
+// lanes j >= 8 row 16 - a, in the second the reverse.  Wave 3 holds rows 0 and 8 whole (g = 0, 1;
+// row 8 mirrors within itself, row 0 is the exception below) and the pair (7, 9).  The index
+// within the row stays j, a wave still owns four rows, and the rows of a pair lie an even number
+// of rows (a multiple of 2 * 544 dwords) apart, so the LDS bank pattern is the plain layout's.
+constexpr int ols_rg_row(int t) {
+    const int w = t >> 6, g = (t >> 4) & 3, j = t & 15;
+    if (w == 3 && g < 2) return 8 * g;
+    const int a = w == 3 ? 7 : 2 * w + 1 + (g >> 1);
+    return (g & 1) != (j >> 3) ? 16 - a : a;
+}
+// the same map for the kernel, without a branch: the rows of the two halves (j < 8, j >= 8) of the
+// sixteen 16-lane groups, four bits each, in two 64-bit constants
+constexpr unsigned long long ols_rg_pack(int half) {
+    unsigned long long v = 0;
+    for (int grp = 0; grp < 16; ++grp) v |= (unsigned long long)ols_rg_row(16 * grp + 8 * half) << (4 * grp);
+    return v;
+}
+constexpr int ols_rg_row_packed(int t) {
+    return (int)(((t & 8) ? ols_rg_pack(1) : ols_rg_pack(0)) >> (4 * (t >> 4))) & 15;
+}
+constexpr bool ols_rg_packed_is_the_map() {
+    for (int t = 0; t < 256; ++t)
+        if (ols_rg_row_packed(t) != ols_rg_row(t)) return false;
+    return true;
+}
+static_assert(ols_rg_packed_is_the_map(), "the packed form is ols_rg_row");
+constexpr bool ols_rg_bijective() {
+    bool seen[256] = {};
+    for (int t = 0; t < 256; ++t) {
+        const int r = ols_rg_row(t);
+        if (r < 0 || r > 15 || seen[16 * r + (t & 15)]) return false;
+        seen[16 * r + (t & 15)] = true;
+    }
+    return true;
+}
+constexpr bool ols_rg_four_rows_per_wave() {
+    for (int w = 0; w < 4; ++w) {
+        int rows = 0, count = 0;
+        for (int l = 0; l < 64; ++l) rows |= 1 << ols_rg_row(64 * w + l);
+        for (int r = 0; r < 16; ++r) count += (rows >> r) & 1;
+        if (count != 4) return false;
+    }
+    return true;
+}
+constexpr bool ols_rg_mirror_in_dpp_row() {
+    for (int t = 0; t < 256; ++t) {
+        const int r = ols_rg_row(t), m = (t & ~15) | (15 - (t & 15));  // row_mirror's source lane
+        if (r != 0 && (ols_rg_row(m) != 16 - r || (m & 15) != 15 - (t & 15))) return false;
+    }
+    return true;
+}
+static_assert(ols_rg_bijective(), "the lane map covers 16 rows x 16 indices once");
+static_assert(ols_rg_four_rows_per_wave(), "P2 - P4 of a wave touch four rows (wave-level hand-offs)");
+static_assert(ols_rg_mirror_in_dpp_row(), "row != 0: position 15 - j of the group holds (16 - row, 15 - k1)");
+
+// a * conj(b) with the operations of pmul(a, {b.x, -b.y}), bit for bit: what the boundary
+// instance computes from the full table, whose entry is that conjugate
+[[maybe_unused]] __device__ __forceinline__ f2 pmul_cj(f2 a, f2 b) {
+    f2 t, r;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0]" : "=v"(t) : "v"(a), "v"(b));
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] neg_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(b), "v"(t));
+    return r;
+}
+
+// The two bins of one k-pair whose spectrum values are the conjugates of the MIRROR lane's pair m
+// (halves swapped): r0 = a0 * conj(m.zw), r1 = a1 * conj(m.xy), m read from the lane at the
+// mirrored position of the 16-lane row through a row_mirror DPP operand -- no copy of the 16
+// dwords (lab form 1; the product ships form 2 below).  Per component the operations of pmul_cj (one multiply, one fused multiply-add, the same
+// operands), so the bits are those of a pmul against the full table.  Every lane of the wave must
+// be active (a DPP read of an inactive lane writes nothing); the s_nop covers the DPP
+// read-after-VALU-write hazard should the compiler have moved m just before.
+[[maybe_unused]] __device__ __forceinline__ void mirror_products_vop2(f2 a0, f2 a1, float4 m, f2& r0, f2& r1) {
+    float x0, y0, x1, y1;
+#define SDSP_RM " row_mirror row_mask:0xf bank_mask:0xf\n\t"
+    asm("s_nop 1\n\t"
+        "v_mul_f32_dpp %0, %9, %5" SDSP_RM     // x0 = b.y a0.y      (b = m.zw of the mirror lane)
+        "v_mul_f32_dpp %1, %8, %5" SDSP_RM     // y0 = b.x a0.y
+        "v_mul_f32_dpp %2, %11, %7" SDSP_RM    // x1 = c.y a1.y      (c = m.xy of the mirror lane)
+        "v_mul_f32_dpp %3, %10, %7" SDSP_RM    // y1 = c.x a1.y
+        "v_fmac_f32_dpp %0, %8, %4" SDSP_RM    // x0 += b.x a0.x
+        "v_fmac_f32_dpp %1, -%9, %4" SDSP_RM   // y0 -= b.y a0.x
+        "v_fmac_f32_dpp %2, %10, %6" SDSP_RM   // x1 += c.x a1.x
+        "v_fmac_f32_dpp %3, -%11, %6 row_mirror row_mask:0xf bank_mask:0xf"
+        : "=&v"(x0), "=&v"(y0), "=&v"(x1), "=&v"(y1)
+        : "v"(a0.x), "v"(a0.y), "v"(a1.x), "v"(a1.y), "v"(m.z), "v"(m.w), "v"(m.x), "v"(m.y));
+#undef SDSP_RM
+    r0 = f2{x0, y0};
+    r1 = f2{x1, y1};
+}
+
+// form 2 (the product's mirror_products): the mirror lane's pair copied by four v_mov_b32 with the
+// same DPP operand, then the packed products (pmul_cj): 4 + 4 instructions per pair against 8
+[[maybe_unused]] __device__ __forceinline__ void mirror_products_mov(f2 a0, f2 a1, float4 m, f2& r0, f2& r1) {
+    float bx, by, cx, cy;
+    asm("s_nop 1\n\t"
+        "v_mov_b32_dpp %0, %4 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_mov_b32_dpp %1, %5 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_mov_b32_dpp %2, %6 row_mirror row_mask:0xf bank_mask:0xf\n\t"
+        "v_mov_b32_dpp %3, %7 row_mirror row_mask:0xf bank_mask:0xf"
+        : "=&v"(bx), "=&v"(by), "=&v"(cx), "=&v"(cy)
+        : "v"(m.z), "v"(m.w), "v"(m.x), "v"(m.y));
+    r0 = pmul_cj(a0, f2{bx, by});
+    r1 = pmul_cj(a1, f2{cx, cy});
+}
+
 // lab clock stamp i of variant 262144 (SDSP_OLS_STAMPS builds only): s_memtime into st[i], pinned
 // in program order by scheduling barriers (which also keep the compiler from moving code across
 // the stamp: the perturbation is measured by running the stamped instance against variant 24)
@@ -162,7 +275,13 @@ constexpr int kStampWords = 16;  // u64 per sampled workgroup: memtime, realtime
 // 49152 = the round-3 kernel); 131072 with 4: the HBM-only pattern in 16-byte lanes (the NCO
 // kernel's shape); 262144 clock stamps (lab builds that define SDSP_OLS_STAMPS only: every 32nd
 // workgroup records s_memtime / s_memrealtime at entry and exit into g_ols_stamps, a buffer no
-// other code reads; the in-kernel clock of MI355X_MICROARCH.md "DVFS give-back" item 6).
+// other code reads; the in-kernel clock of MI355X_MICROARCH.md "DVFS give-back" item 6);
+// real g, half the spectrum loads (the product's REALG instances, kern_fir_ols_os.hip): 1048576 the
+// rows of P2 - P4 dealt by ols_rg_row, four spectrum loads per lane from the half table, the bins
+// k2 >= 8 as products with the mirror lane's registers through a row_mirror DPP operand
+// (mirror_products_vop2); 8388608 the same with the mirror lane's registers copied by
+// v_mov_b32_dpp and packed products (mirror_products_mov: 8388632 is the form of the product's
+// <true, false, false, true>).
 //
 // xw / yw point at the segment's window x[base, base + 4096) of its channel (the callers add the
 // segment's offset once, for both); base, n, hist, new_hist and Lm1 are read by EDGE only.  st: the
@@ -193,7 +312,7 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
     const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)yw, (short)0, nrec, kBufWord3);
     const auto rt = __builtin_amdgcn_make_buffer_rsrc((void*)tb, (short)0, kOlsOsTabF4 * 16, kBufWord3);
     const auto rh = __builtin_amdgcn_make_buffer_rsrc((void*)Hs, (short)0,
-                                                      (ABL & 268435456) ? 4 * kOlsHalfRow * 16 : 2048 * 16, kBufWord3);
+                                                      (ABL & (268435456 | 1048576 | 8388608)) ? 4 * kOlsHalfRow * 16 : 2048 * 16, kBufWord3);
     constexpr int kLdAux = (ABL & 16384) ? 0 : 2;  // nontemporal (aux 2)
     // twiddle bases: column t of W4096, row lo4 of W256 (runtime.cpp ols_build), requested
     // before the segment's rows (L2 hits that land while the rows stream in)
@@ -370,13 +489,26 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
     };
 
     constexpr bool kReal = (ABL & 268435456) != 0;
+    constexpr int kRg = (ABL & 1048576) ? 1 : (ABL & 8388608) ? 2 : 0;  // half the spectrum loads, DPP form 1 / 2
+    const int row = kRg ? ols_rg_row_packed(t) : hi4;                  // the lane's row in P2 - P4
     auto load_h = [&] {
         // hq: the spectrum slice of lane (k0, k1) = t for P3, k-pair major.  kOlsRealTaps (real taps,
         // H[N - k] = conj H[k]): pairs p < 4 from the half table at lane t, pairs p >= 4 as the
         // conjugates of pair 7 - p of the mirror lane (16 - k0, 15 - k1) (k0 = 0: (0, 16 - k1); lane
         // (0, 0): the table's tail entry), halves swapped -- a 16 KB table instead of 32 KB, read with
         // the same eight loads (runtime.cpp ols_build)
-        if constexpr (kReal) {
+        if constexpr (kRg != 0) {
+            // the lane's own pairs p < 4; row 0 alone also its mirror's (0, 16 - k1), as below
+#pragma unroll
+            for (int p = 0; p < 4 && first; ++p)
+                hq[p] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rh, 16 * (16 * row + lo4), 16 * kOlsHalfRow * p, 0));
+            if (row == 0 && first) {
+                const int ml = lo4 ? 16 - lo4 : 256;
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+                    hq[7 - p] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rh, 16 * ml, 16 * kOlsHalfRow * p, 0));
+            }
+        } else if constexpr (kReal) {
             const int k0 = hi4, k1 = lo4;
             const int ml = k0 ? 16 * (16 - k0) + (15 - k1) : (k1 ? 16 - k1 : 256);
 #pragma unroll
@@ -417,7 +549,7 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
 
     phase_mark<ABL, 1>();
     // P2: lane (k0 = hi4, n0 = lo4): DFT16 n1 -> k1, * W256^(n0 k1) -> (k0, 16 k1 + n0)
-    f2* r2 = img + hi4 * kRow + lo4;  // (hi4, 16 j + lo4) at r2[17 j]
+    f2* r2 = img + row * kRow + lo4;  // (row, 16 j + lo4) at r2[17 j]
 #pragma unroll
     for (int j = 0; j < 16; ++j) v[j] = r2[17 * j];
     if constexpr ((ABL & (1073741824 | 536870912)) == 0) load_h();
@@ -432,7 +564,7 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
     phase_mark<ABL, 2>();
     // P3: lane (k0 = hi4, k1 = lo4) over n0: DFT16 n0 -> k2, * H, IDFT16 k2 -> n0, * conj W256^(k1 n0)
     {
-        f2* r3 = img + hi4 * kRow + 17 * lo4;  // (hi4, 16 lo4 + j) at r3[j]
+        f2* r3 = img + row * kRow + 17 * lo4;  // (row, 16 lo4 + j) at r3[j]
 #pragma unroll
         for (int j = 0; j < 16; ++j) v[j] = r3[j];
         dft(v);
@@ -445,13 +577,28 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
 #endif
         f2 u[16];
 #pragma unroll
-        for (int p = 0; p < 8; ++p) {
+        for (int p = 0; p < (kRg ? 4 : 8); ++p) {
             if (kReal && p >= 4) {  // {conj m.zw, conj m.xy} of the mirror's pair
                 u[2 * p] = pmulc(v[kout(2 * p)], f2{hq[p].z, hq[p].w});
                 u[2 * p + 1] = pmulc(v[kout(2 * p + 1)], f2{hq[p].x, hq[p].y});
             } else {
                 u[2 * p] = pmul(v[kout(2 * p)], f2{hq[p].x, hq[p].y});
                 u[2 * p + 1] = pmul(v[kout(2 * p + 1)], f2{hq[p].z, hq[p].w});
+            }
+        }
+        if constexpr (kRg != 0) {
+            // all lanes through DPP (it needs the whole wave), then row 0 over its own loads
+#pragma unroll
+            for (int p = 4; p < 8; ++p) {
+                if constexpr (kRg == 1) mirror_products_vop2(v[kout(2 * p)], v[kout(2 * p + 1)], hq[7 - p], u[2 * p], u[2 * p + 1]);
+                else mirror_products_mov(v[kout(2 * p)], v[kout(2 * p + 1)], hq[7 - p], u[2 * p], u[2 * p + 1]);
+            }
+            if (row == 0) {
+#pragma unroll
+                for (int p = 4; p < 8; ++p) {
+                    u[2 * p] = pmul_cj(v[kout(2 * p)], f2{hq[p].z, hq[p].w});
+                    u[2 * p + 1] = pmul_cj(v[kout(2 * p + 1)], f2{hq[p].x, hq[p].y});
+                }
             }
         }
         idft(u);
@@ -676,7 +823,7 @@ hipError_t launch_fir_ols_os_t(const OlsPlan& p, const void* x, const void* hist
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || hi <= lo) return e;
     // the interior kernel's spectrum table: the half table for real taps (ABL 268435456)
-    const float4* hs = (const float4*)((ABL & 268435456) ? p.d_hhalf : p.d_pkt);
+    const float4* hs = (const float4*)((ABL & (268435456 | 1048576 | 8388608)) ? p.d_hhalf : p.d_pkt);
     if constexpr (ols_round6_prologue(ABL)) {
         if (round6 || ols_long_list_only(ABL)) {
             hipLaunchKernelGGL((fir_ols_os_kernel<ABL, false>), dim3((unsigned)(8 * qg), (unsigned)channels), dim3(256),
