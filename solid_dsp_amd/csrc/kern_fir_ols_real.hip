@@ -7,10 +7,10 @@
 //     conv(a + i b, g) = conv(a, g) + i conv(b, g),
 // so one 4096-point complex transform filters two real windows: pair p packs the adjacent
 // segments A = 2p and B = 2p + 1 as z = A + i B, runs the transform of the c32 kernel on z
-// (phases P1..P5 below are those of ols_os_segment: pdft16f, the C/D/E/F twiddle bases of
-// d_ostab, the spectrum of d_pkt, the 34 KB aliased LDS image, 4 workgroups per CU), and stores
-// rows >= h2 of Re to A's outputs and of Im to B's.  The phase code is a copy, not a shared
-// header, so that the c32 translation unit stays instruction for instruction what it was.
+// (ols_os_transform of sdsp_ols_os.hpp, the one copy both kernels share: pdft16f, the C/D/E/F
+// twiddle bases of d_ostab, the spectrum of d_pkt, the 34 KB aliased LDS image, 4 workgroups per
+// CU), and stores rows >= h2 of Re to A's outputs and of Im to B's.  The taps are real, but this
+// kernel runs the full-table form of the transform, not its half-spectrum (REALG) form.
 //
 // Adjacent segments pair up (not distant halves of the call): B's halo is A's tail and A's halo
 // is the previous pair's tail, which the same XCD has just read (workgroup b runs on XCD b % 8
@@ -39,133 +39,16 @@
 // Numerics: the rounding error of a real segment is relative to the energy of its pair.
 // Deterministic for a given sequence of calls, but not bit-invariant to where the stream is cut
 // into calls (the cut decides which segments pair).
-#include "sdsp_device.hpp"
-#include "sdsp_kernels.hpp"
-#include "sdsp_pk.hpp"
+#include "sdsp_ols_os.hpp"
 
 namespace sdsp {
 
-using namespace pk;
-
 namespace {
 
-constexpr int kRow = 272;
-
-constexpr int kBufWord3 = 0x00020000;  // raw buffer descriptor word 3 (gfx9 family)
-constexpr int kNT = 2;                 // nontemporal cache policy of a buffer access
 constexpr int kOutOfRange = 0x7ffffff0;  // a buffer offset past every descriptor here: loads return 0
-
-typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-
-// see kern_fir_ols_os.hip: P2 -> P3 -> P4 stay inside one wave
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// x = D_{k>>2} C_{k&3} for C_b = c[b-1], D_a = d[a-1] (k = 0 -> 1)
-__device__ __forceinline__ f2 tw_pair(const f2 (&c)[3], const f2 (&d)[3], int k) {
-    const int a = k >> 2, b = k & 3;
-    if (a == 0) return b == 0 ? f2{1.0f, 0.0f} : c[b - 1];
-    if (b == 0) return d[a - 1];
-    return pmul(d[a - 1], c[b - 1]);
-}
-
-// lane pair (2c, 2c + 1) exchange of kern_fir_ols_os.hip: even lanes lo = a, odd lanes lo = the
-// partner's b; odd lanes hi = b, even lanes hi = the partner's a
-__device__ __forceinline__ void pair_exchange(f2 a, f2 b, f2& lo, f2& hi) {
-    float l0, l1, h0, h1;
-    asm("s_nop 1\n\t"
-        "s_mov_b32 vcc_lo, 0x55555555\n\t"
-        "s_mov_b32 vcc_hi, 0x55555555\n\t"
-        "v_cndmask_b32_dpp %0, %6, %4, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %1, %7, %5, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_not_b64 vcc, vcc\n\t"
-        "v_cndmask_b32_dpp %2, %4, %6, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "v_cndmask_b32_dpp %3, %5, %7, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
-        : "=&v"(l0), "=&v"(l1), "=&v"(h0), "=&v"(h1)
-        : "v"(a.x), "v"(a.y), "v"(b.x), "v"(b.y)
-        : "vcc");
-    lo = f2{l0, l1};
-    hi = f2{h0, h1};
-}
 
 template <int POL> __device__ __forceinline__ float ld32(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, POL));
-}
-
-// The transform between "rows loaded" and "rows ready to store" (P1..P5 of ols_os_segment):
-// v[r] = z(256 r + t) in, circular convolution row n2 at v[kout(n2)] out.
-__device__ __forceinline__ void ols_real_transform(f2 (&v)[16], const float4 cd, const float4 ef,
-                                                   __amdgpu_buffer_rsrc_t rh, f2* img, int t) {
-    const int hi4 = t >> 4, lo4 = t & 15;
-    // the first power of each base from L2, the others as products (W^2 = W W, W^3 = W^2 W)
-    f2 Cb[3], Da[3], Eb[3], Fa[3];
-    {
-        const f2 c1 = f2{cd.x, cd.y}, d1 = f2{cd.z, cd.w}, e1 = f2{ef.x, ef.y}, f1 = f2{ef.z, ef.w};
-        const f2 c2 = pmul(c1, c1), d2 = pmul(d1, d1), e2 = pmul(e1, e1), f2_ = pmul(f1, f1);
-        Cb[0] = c1, Cb[1] = c2, Cb[2] = pmul(c2, c1);
-        Da[0] = d1, Da[1] = d2, Da[2] = pmul(d2, d1);
-        Eb[0] = e1, Eb[1] = e2, Eb[2] = pmul(e2, e1);
-        Fa[0] = f1, Fa[1] = f2_, Fa[2] = pmul(f2_, f1);
-    }
-    f2* col = img + t + (t >> 4);  // (r, t) at col[r * kRow]
-
-    // P1: DFT16 n2 -> k0, * W4096^(t k0) -> (k0, t)
-    pdft16f<false>(v);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) col[k * kRow] = k == 0 ? v[0] : pmul(v[kout(k)], tw_pair(Cb, Da, k));
-    __syncthreads();
-
-    // P2: lane (k0 = hi4, n0 = lo4): DFT16 n1 -> k1, * W256^(n0 k1) -> (k0, 16 k1 + n0)
-    f2* r2 = img + hi4 * kRow + lo4;  // (hi4, 16 j + lo4) at r2[17 j]
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = r2[17 * j];
-    float4 hq[8];  // the spectrum slice of lane (k0, k1) = t for P3, k-pair major
-#pragma unroll
-    for (int p = 0; p < 8; ++p) hq[p] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rh, 16 * t, 4096 * p, 0));
-    f2 w2[16];  // W256^(lo4 k), used by P2 (n0 = lo4) and P3 (k1 = lo4)
-#pragma unroll
-    for (int k = 1; k < 16; ++k) w2[k] = tw_pair(Eb, Fa, k);
-    pdft16f<false>(v);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) r2[17 * k] = k == 0 ? v[0] : pmul(v[kout(k)], w2[k]);
-    wave_sync();
-
-    // P3: lane (k0 = hi4, k1 = lo4) over n0: DFT16 n0 -> k2, * H, IDFT16 k2 -> n0, * conj W256^(k1 n0)
-    {
-        f2* r3 = img + hi4 * kRow + 17 * lo4;  // (hi4, 16 lo4 + j) at r3[j]
-#pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] = r3[j];
-        pdft16f<false>(v);
-        f2 u[16];
-#pragma unroll
-        for (int p = 0; p < 8; ++p) {
-            u[2 * p] = pmul(v[kout(2 * p)], f2{hq[p].x, hq[p].y});
-            u[2 * p + 1] = pmul(v[kout(2 * p + 1)], f2{hq[p].z, hq[p].w});
-        }
-        pdft16f<true>(u);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) r3[j] = j == 0 ? u[kout(0)] : pmulc(u[kout(j)], w2[j]);
-    }
-    wave_sync();
-
-    // P4: lane (k0 = hi4, n0 = lo4): IDFT16 k1 -> n1 -> (k0, 16 n1 + n0)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = r2[17 * j];
-    pdft16f<true>(v);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) r2[17 * k] = v[kout(k)];
-    __syncthreads();
-
-    // P5: lane t: * conj W4096^(t k0), IDFT16 k0 -> n2; row n2 at v[kout(n2)].  The bases are
-    // made opaque first so the products are recomputed here rather than kept live from P1.
-#pragma unroll
-    for (int i = 0; i < 3; ++i) asm volatile("" : "+v"(Cb[i]), "+v"(Da[i]));
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v[k] = k == 0 ? col[0] : pmulc(col[k * kRow], tw_pair(Cb, Da, k));
-    pdft16f<true>(v);
 }
 
 }  // namespace
@@ -200,7 +83,6 @@ fir_ols_real_kernel(const float* __restrict__ x, const float* __restrict__ hist,
     x += ch * n;
     y += ch * n;
     const auto rt = __builtin_amdgcn_make_buffer_rsrc((void*)tb, (short)0, kOlsOsTabF4 * 16, kBufWord3);
-    const auto rh = __builtin_amdgcn_make_buffer_rsrc((void*)Hs, (short)0, 2048 * 16, kBufWord3);
     // twiddle bases: {C1, D1} of column t and {E1, F1} of row t & 15, requested before the rows
     const float4 cd = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rt, 16 * t, 16 * kOlsOsTabCD, 0));
     const float4 ef = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rt, 16 * (t & 15), 16 * kOlsOsTabEF, 0));
@@ -256,7 +138,7 @@ fir_ols_real_kernel(const float* __restrict__ x, const float* __restrict__ hist,
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = f2{w[0][r], w[1][r]};
-        ols_real_transform(v, cd, ef, rh, img, t);
+        ols_os_transform<false>(v, cd, ef, Hs, img, t, t & 15);
         // rows >= h2 start at seg V + 256 (r - h2) >= 0; positions past the stream fall outside
         // the descriptor (dropped)
 #pragma unroll
@@ -287,7 +169,7 @@ fir_ols_real_kernel(const float* __restrict__ x, const float* __restrict__ hist,
             }
 #pragma unroll
             for (int k = 0; k < 8; ++k) pair_exchange(f2{qa[k].x, qb[k].x}, f2{qa[k].y, qb[k].y}, v[k], v[8 + k]);
-            ols_real_transform(v, cd, ef, rh, img, t);
+            ols_os_transform<false>(v, cd, ef, Hs, img, t, t & 15);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 f2 a, b;  // z of columns (2c, 2c + 1) of row k + 8h
@@ -311,7 +193,7 @@ fir_ols_real_kernel(const float* __restrict__ x, const float* __restrict__ hist,
                 }
             }
             if constexpr (HALO1) v[0].y = v[15].x;  // B's halo is A's last row
-            ols_real_transform(v, cd, ef, rh, img, t);
+            ols_os_transform<false>(v, cd, ef, Hs, img, t, t & 15);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 if (r >= h2) {

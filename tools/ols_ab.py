@@ -3,6 +3,11 @@
 
   python tools/ols_ab.py            # one-shot (0) vs persistent packed (1) vs scalar (2)
   OLS_KERNELS=0,1 OLS_ROUNDS=20 python tools/ols_ab.py
+  OLS_TAPS=700 OLS_COMPLEX_TAPS=1 OLS_KERNELS=0,3 python tools/ols_ab.py
+
+OLS_TAPS (default 256, one halo row) sets the tap count: above 257 the interior kernels are the
+generic-halo instances.  OLS_COMPLEX_TAPS=1 turns the taps by a complex exponential (complex64
+coefficients), so the handle has no half spectrum and the kernels load the full table.
 """
 import json
 import os
@@ -21,13 +26,16 @@ def main(rounds=int(os.environ.get("OLS_ROUNDS", "12")), log2n=30):
     from solid_dsp_amd import FIRFilter
     from solid_dsp_amd.filter import firdes
     n = 1 << log2n
-    h = firdes.firdes_kaiser(256, 0.1, 80.0, 0.0).astype(np.float32)
+    taps = int(os.environ.get("OLS_TAPS", "256"))
+    h = firdes.firdes_kaiser(taps, 0.1, 80.0, 0.0).astype(np.float32)
+    if os.environ.get("OLS_COMPLEX_TAPS", "0") == "1":
+        h = (h * np.exp(2j * np.pi * 0.05 * np.arange(taps))).astype(np.complex64)
     d_in = torch.empty(n, dtype=torch.complex64, device="cuda")
     sd.lib().sdsp_synth_f32_device(d_in.data_ptr(), 20250226, 0, 0, 2 * n, None)
     kernels = [int(k) for k in os.environ.get("OLS_KERNELS", "0,1,2").split(",")]
     variants = {}
     for k in kernels:
-        f = FIRFilter(h, np.float32(0.2), sample_dtype=np.complex64, algo=sd.ALGO_FFT)
+        f = FIRFilter(h, h.dtype.type(0.2), sample_dtype=np.complex64, algo=sd.ALGO_FFT)
         assert sd.lib().sdsp_fir_set_tuning(f._h, TUNE_OLS_KERNEL, k) == 0
         variants[f"kernel{k}"] = f
     s = torch.cuda.current_stream()
