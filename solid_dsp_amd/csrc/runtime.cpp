@@ -50,18 +50,8 @@ int device_status(hipError_t e, const char* what) {
     set_error(std::string(what) + ": " + hipGetErrorString(e));
     return e == hipErrorOutOfMemory ? SDSP_E_OUT_OF_MEMORY : SDSP_E_DEVICE;
 }
-#define SDSP_TRY(expr, what)                              \
-    do {                                                  \
-        hipError_t _e = (expr);                           \
-        if (_e != hipSuccess) return device_status(_e, what); \
-    } while (0)
 
-struct DeviceInfo {
-    bool ok = false;
-    int cus = 256;
-};
-
-static int check_device(int device, DeviceInfo* info) {
+int check_device(int device, int* cus) {
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
         set_error("no HIP device visible (libsdsp has no CPU execution path)");
@@ -80,25 +70,9 @@ static int check_device(int device, DeviceInfo* info) {
         set_error(std::string("libsdsp is built for gfx950; device is ") + prop.gcnArchName);
         return SDSP_E_NO_DEVICE;
     }
-    info->ok = true;
-    info->cus = prop.multiProcessorCount;
+    if (cus) *cus = prop.multiProcessorCount;
     return SDSP_OK;
 }
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int d) {
-        (void)hipGetDevice(&prev);
-        if (prev != d) (void)hipSetDevice(d);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-static hipStream_t pick(void* user, hipStream_t own) { return user ? (hipStream_t)user : own; }
 
 }  // namespace sdsp
 
@@ -107,20 +81,16 @@ using namespace sdsp;
 // ===========================================================================
 // FIR / decimating FIR
 // ===========================================================================
-struct sdsp_fir {
-    int dtype = 0, device = 0, cus = 256;
+struct sdsp_fir : HandleCore {
+    int dtype = 0, cus = 256;
     mutable unsigned long long device_ops = 0;  // sdsp_fir_device_ops
     size_t L = 0, M = 1, channels = 1;
     std::vector<unsigned char> taps;   // original order (host copy for coefficients / design queries)
     std::vector<unsigned char> scale;  // one Coef
     DevBuf d_taps_rev;                 // cr[i] = h[L-1-i]  (DotProduct REVERSE, dot_product/mod.rs:73-81)
-    DevBuf d_hist[2];                  // [channels][L-1] oldest first
-    int cur = 0;
+    PingPong hist;                     // [channels][L-1] oldest first
     size_t ci = 0;                     // DecimatingFIRFilter::current_item (decim.rs:7)
     int algo = SDSP_ALGO_EXACT;        // reference-order kernel unless the caller opts in (sdsp.h)
-    hipStream_t stream = nullptr;
-    mutable StreamFence fence;         // last stream an execute call was queued on
-    DevBuf stage_in, stage_out;
     HostMapped step_out;  // per-sample execute on the device: output at [0, 16), completion flag at [16, 20)
     unsigned step_seq = 0;
     // host delay line for per-sample calls and small host blocks (runtime_host_step below):
@@ -128,7 +98,7 @@ struct sdsp_fir {
     std::vector<unsigned char> hbuf;
     size_t hpos = 0;
     bool host_valid = false;  // hbuf holds the current window (single-channel handles only)
-    bool dev_stale = false;   // the host consumed samples after d_hist[cur] was last written
+    bool dev_stale = false;   // the host consumed samples after hist.front() was last written
     int host_step = 1;        // SDSP_TUNE_HOST_STEP
     size_t host_macs = 1u << 16;  // host blocks: n * L up to this many multiply-adds
     // overlap-save plan
@@ -143,14 +113,9 @@ namespace {
 
 int fir_alloc_state(sdsp_fir* h) {
     SDSP_TRY(h->fence.wait(), "wait for queued work");
-    const size_t hb = h->channels * (h->L - 1) * sample_bytes(h->dtype);
-    for (int i = 0; i < 2; ++i) {
-        SDSP_TRY(h->d_hist[i].ensure(hb), "alloc history");
-        if (hb) SDSP_TRY(hipMemsetAsync(h->d_hist[i].p, 0, hb, h->stream), "zero history");
-    }
-    h->cur = 0;
+    SDSP_TRY(h->hist.reset(h->channels * (h->L - 1) * sample_bytes(h->dtype), h->stream), "zero history");
     h->ci = 0;
-    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
+    if (int st = h->quiesce()) return st;
     const size_t lm1 = h->L - 1, sb = sample_bytes(h->dtype);
     h->hbuf.assign(2 * lm1 * sb, 0);  // the zeroed window, both copies
     h->hpos = 0;
@@ -363,15 +328,14 @@ int fir_create_common(sdsp_fir** out, int dtype, const void* taps, size_t len, c
         set_error("tap count too large");
         return SDSP_E_INVALID_ARGUMENT;
     }
-    DeviceInfo info;
-    int st = check_device(device, &info);
+    int cus = 256;
+    int st = check_device(device, &cus);
     if (st) return st;
     DeviceGuard g(device);
     sdsp_fir* h = new sdsp_fir();
     h->dtype = dtype;
-    h->device = device;
     h->algo = default_algo();
-    h->cus = info.cus;
+    h->cus = cus;
     h->L = len;
     h->M = M;
     const size_t cb = coef_bytes(dtype);
@@ -379,7 +343,7 @@ int fir_create_common(sdsp_fir** out, int dtype, const void* taps, size_t len, c
     h->scale.assign((const unsigned char*)scale, (const unsigned char*)scale + cb);
     std::vector<unsigned char> rev(len * cb);
     for (size_t i = 0; i < len; ++i) std::memcpy(&rev[i * cb], &h->taps[(len - 1 - i) * cb], cb);
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    hipError_t e = h->open(device);
     if (e == hipSuccess) e = h->d_taps_rev.ensure(rev.size());
     if (e == hipSuccess) e = hipMemcpy(h->d_taps_rev.p, rev.data(), rev.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -481,7 +445,7 @@ int host_pull(sdsp_fir* h) {
     h->hbuf.resize(2 * lm1 * sb);
     ++h->device_ops;
     if (lm1) {
-        SDSP_TRY(hipMemcpy(h->hbuf.data(), h->d_hist[h->cur].p, lm1 * sb, hipMemcpyDeviceToHost), "pull history");
+        SDSP_TRY(hipMemcpy(h->hbuf.data(), h->hist.front(), lm1 * sb, hipMemcpyDeviceToHost), "pull history");
         std::memcpy(h->hbuf.data() + lm1 * sb, h->hbuf.data(), lm1 * sb);
     }
     h->hpos = 0;
@@ -490,7 +454,7 @@ int host_pull(sdsp_fir* h) {
 }
 
 // the device history := the host window (before device work after host steps).  No
-// kernel can be reading d_hist here: host steps start only after host_pull's
+// kernel can be reading hist here: host steps start only after host_pull's
 // synchronisation, a synchronising host call, or a state reset.
 int host_flush(const sdsp_fir* hc) {
     sdsp_fir* h = const_cast<sdsp_fir*>(hc);
@@ -498,7 +462,7 @@ int host_flush(const sdsp_fir* hc) {
     ++h->device_ops;
     const size_t lm1 = h->L - 1, sb = sample_bytes(h->dtype);
     if (lm1)
-        SDSP_TRY(hipMemcpy(h->d_hist[h->cur].p, h->hbuf.data() + h->hpos * sb, lm1 * sb, hipMemcpyHostToDevice),
+        SDSP_TRY(hipMemcpy(h->hist.front(), h->hbuf.data() + h->hpos * sb, lm1 * sb, hipMemcpyHostToDevice),
                  "flush history");
     h->dev_stale = false;
     return SDSP_OK;
@@ -558,11 +522,11 @@ int fir_step_device(sdsp_fir* h, const void* sample, void* out, size_t* n_out, b
     unsigned* flag_h = reinterpret_cast<unsigned*>((char*)h->step_out.host + 16);
     unsigned seq = ++h->step_seq;
     if (seq == 0) seq = h->step_seq = 1;  // the flag's initial 0 never matches
-    FirStepArgs a{sample, h->d_hist[h->cur].p, h->d_hist[h->cur ^ 1].p, h->d_taps_rev.p, h->scale.data(),
+    FirStepArgs a{sample, h->hist.front(), h->hist.back(), h->d_taps_rev.p, h->scale.data(),
                   h->step_out.dev, reinterpret_cast<unsigned*>((char*)h->step_out.dev + 16), seq, (int)h->L - 1,
                   (int)h->L, emit, h->algo != SDSP_ALGO_FMA};
     SDSP_TRY(launch_fir_step(h->dtype, a, h->stream), "fir step");
-    h->cur ^= 1;
+    h->hist.flip();
     h->ci = (h->ci + 1) % h->M;
     h->host_valid = false;
     // the flag is released after the whole workgroup's delay-line stores; the fence orders any
@@ -612,29 +576,7 @@ int sdsp_decim_create(sdsp_fir** out, int dtype, const void* taps, size_t len, c
     return fir_create_common(out, dtype, taps, len, scale, decimation, device);
 }
 
-void sdsp_fir_destroy(sdsp_fir* h) {
-    if (!h) return;
-    {
-        DeviceGuard g(h->device);
-        (void)h->fence.wait();  // work queued on a caller stream may still read the tables / history
-        if (h->stream) {
-            (void)hipStreamSynchronize(h->stream);
-            (void)hipStreamDestroy(h->stream);
-        }
-        h->d_taps_rev.release();
-        h->d_hist[0].release();
-        h->d_hist[1].release();
-        h->stage_in.release();
-        h->stage_out.release();
-        h->d_H.release();
-        h->d_tw1.release();
-        h->d_tw2.release();
-        h->d_pkt.release();
-        h->d_ostab.release();
-        h->d_hhalf.release();
-    }
-    delete h;
-}
+void sdsp_fir_destroy(sdsp_fir* h) { destroy_handle(h); }
 
 int sdsp_fir_set_channels(sdsp_fir* h, size_t channels) {
     if (!h || channels == 0) return SDSP_E_INVALID_ARGUMENT;
@@ -711,12 +653,10 @@ int sdsp_fir_clone(const sdsp_fir* h, sdsp_fir** out) {
     c->ols_kernel = h->ols_kernel;
     c->decim_seg = h->decim_seg;
     const size_t hb = h->channels * (h->L - 1) * sample_bytes(h->dtype);
-    SDSP_TRY(h->fence.wait(), "wait for queued work");
-    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
-    st = host_flush(h);
+    st = h->quiesce();
+    if (!st) st = host_flush(h);
     if (st) return st;
-    if (hb) SDSP_TRY(hipMemcpy(c->d_hist[0].p, h->d_hist[h->cur].p, hb, hipMemcpyDeviceToDevice), "clone state");
-    c->cur = 0;
+    if (hb) SDSP_TRY(hipMemcpy(c->hist.front(), h->hist.front(), hb, hipMemcpyDeviceToDevice), "clone state");
     c->ci = h->ci;
     c->host_step = h->host_step;
     c->host_macs = h->host_macs;
@@ -774,7 +714,7 @@ int sdsp_fir_execute_block_device(sdsp_fir* h, const void* d_in, size_t n, void*
     h->host_valid = false;  // the input is device-resident: the host window is re-read when needed
     // work queued on another stream (the fence) reads or writes the history this launch uses
     SDSP_TRY(h->fence.order_before(s), "order after queued work");
-    const void* hist = h->d_hist[h->cur].p;
+    const void* hist = h->hist.front();
     bool hist_done = false;  // the overlap-save launch wrote the next history itself
     if (h->M == 1) {
         const int algo = fir_resolve_algo(h, n);
@@ -783,7 +723,7 @@ int sdsp_fir_execute_block_device(sdsp_fir* h, const void* d_in, size_t n, void*
                 int st = ols_build(h);
                 if (st) return st;
             }
-            SDSP_TRY(launch_fir_ols(h->ols, d_in, hist, h->d_hist[h->cur ^ 1].p, d_out, n, (int)h->L, h->channels,
+            SDSP_TRY(launch_fir_ols(h->ols, d_in, hist, h->hist.back(), d_out, n, (int)h->L, h->channels,
                                     h->cus, s, &hist_done),
                      "fir ols");
         } else {
@@ -801,9 +741,9 @@ int sdsp_fir_execute_block_device(sdsp_fir* h, const void* d_in, size_t n, void*
         h->ci = (h->ci + n) % h->M;
     }
     if (!hist_done)
-        SDSP_TRY(launch_hist_update(h->dtype, d_in, hist, h->d_hist[h->cur ^ 1].p, n, (int)h->L - 1, h->channels, s),
+        SDSP_TRY(launch_hist_update(h->dtype, d_in, hist, h->hist.back(), n, (int)h->L - 1, h->channels, s),
                  "history update");
-    h->cur ^= 1;
+    h->hist.flip();
     SDSP_TRY(h->fence.record(s), "record fence");
     return SDSP_OK;
 }
@@ -818,15 +758,11 @@ int sdsp_fir_execute_block(sdsp_fir* h, const void* in, size_t n, void* out, siz
     if (n == 0) return SDSP_OK;
     if (host_eligible(h, n)) return host_run(h, (const unsigned char*)in, n, (unsigned char*)out, nullptr);
     const bool keep = h->host_valid;
-    SDSP_TRY(h->stage_in.ensure(h->channels * n * sb), "stage in");
-    SDSP_TRY(h->stage_out.ensure(h->channels * std::max<size_t>(nout, 1) * sb), "stage out");
-    SDSP_TRY(hipMemcpyAsync(h->stage_in.p, in, h->channels * n * sb, hipMemcpyHostToDevice, h->stream), "H2D");
-    int st = sdsp_fir_execute_block_device(h, h->stage_in.p, n, h->stage_out.p, nullptr, h->stream);
+    int st = h->staged(in, h->channels * n * sb, out, h->channels * nout * sb,
+                       [&](const void* d_in, void* d_out, hipStream_t s) {
+                           return sdsp_fir_execute_block_device(h, d_in, n, d_out, nullptr, s);
+                       });
     if (st) return st;
-    if (nout)
-        SDSP_TRY(hipMemcpyAsync(out, h->stage_out.p, h->channels * nout * sb, hipMemcpyDeviceToHost, h->stream),
-                 "D2H");
-    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
     h->host_valid = keep;  // the host holds the input: move its window on without a read-back
     host_feed(h, (const unsigned char*)in, n);
     return SDSP_OK;
@@ -849,10 +785,10 @@ int sdsp_decim_write(sdsp_fir* h, const void* samples, size_t n) {
     ++h->device_ops;
     SDSP_TRY(h->stage_in.ensure(h->channels * n * sb), "stage in");
     SDSP_TRY(hipMemcpyAsync(h->stage_in.p, samples, h->channels * n * sb, hipMemcpyHostToDevice, h->stream), "H2D");
-    SDSP_TRY(launch_hist_update(h->dtype, h->stage_in.p, h->d_hist[h->cur].p, h->d_hist[h->cur ^ 1].p, n,
+    SDSP_TRY(launch_hist_update(h->dtype, h->stage_in.p, h->hist.front(), h->hist.back(), n,
                                 (int)h->L - 1, h->channels, h->stream),
              "history update");
-    h->cur ^= 1;
+    h->hist.flip();
     h->ci = (h->ci + n) % h->M;
     SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
     host_feed(h, (const unsigned char*)samples, n);
@@ -876,12 +812,11 @@ int sdsp_fir_get_state(const sdsp_fir* h, void* hist, size_t* phase) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     DeviceGuard g(h->device);
     const size_t hb = h->channels * (h->L - 1) * sample_bytes(h->dtype);
-    SDSP_TRY(h->fence.wait(), "wait for queued work");
-    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
+    if (int st = h->quiesce()) return st;
     if (h->dev_stale) {  // the host window is the newer one
         if (hb && hist) std::memcpy(hist, h->hbuf.data() + h->hpos * sample_bytes(h->dtype), hb);
     } else if (hb && hist) {
-        SDSP_TRY(hipMemcpy(hist, h->d_hist[h->cur].p, hb, hipMemcpyDeviceToHost), "get state");
+        SDSP_TRY(hipMemcpy(hist, h->hist.front(), hb, hipMemcpyDeviceToHost), "get state");
     }
     if (phase) *phase = h->ci;
     return SDSP_OK;
@@ -891,9 +826,8 @@ int sdsp_fir_set_state(sdsp_fir* h, const void* hist, size_t phase) {
     if (!h || phase >= h->M) return SDSP_E_INVALID_ARGUMENT;
     DeviceGuard g(h->device);
     const size_t hb = h->channels * (h->L - 1) * sample_bytes(h->dtype);
-    SDSP_TRY(h->fence.wait(), "wait for queued work");
-    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
-    if (hb && hist) SDSP_TRY(hipMemcpy(h->d_hist[h->cur].p, hist, hb, hipMemcpyHostToDevice), "set state");
+    if (int st = h->quiesce()) return st;
+    if (hb && hist) SDSP_TRY(hipMemcpy(h->hist.front(), hist, hb, hipMemcpyHostToDevice), "set state");
     h->ci = phase;
     h->dev_stale = false;
     h->host_valid = false;  // re-read on the next host step
@@ -929,9 +863,7 @@ unsigned long long sdsp_fir_device_ops(const sdsp_fir* h) { return h ? h->device
 int sdsp_fir_synchronize(sdsp_fir* h) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     DeviceGuard g(h->device);
-    SDSP_TRY(h->fence.wait(), "wait for queued work");
-    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    return h->quiesce();
 }
 
 }  // extern "C"
@@ -939,33 +871,23 @@ int sdsp_fir_synchronize(sdsp_fir* h) {
 // ===========================================================================
 // Polyphase filterbank / interpolating FIR
 // ===========================================================================
-struct sdsp_pfb {
-    int dtype = 0, device = 0;
+struct sdsp_pfb : HandleCore {
+    int dtype = 0;
     size_t M = 0, K = 0, channels = 1;
     bool interp = false;
     std::vector<unsigned char> cb;     // [M][K] branch coefficients, stored order
     std::vector<unsigned char> scale;  // kept, never applied (pfb.rs:85-90)
     DevBuf d_cb;
-    DevBuf d_hist[2];  // [channels][K] : the Window(K), oldest first
-    int cur = 0;
+    PingPong hist;  // [channels][K] : the Window(K), oldest first
     int algo = SDSP_ALGO_EXACT;
-    hipStream_t stream = nullptr;
-    mutable StreamFence fence;  // last caller stream an execute call was queued on
-    DevBuf stage_in, stage_out;
 };
 
 namespace {
 
 int pfb_alloc_state(sdsp_pfb* h) {
     SDSP_TRY(h->fence.wait(), "wait for queued work");
-    const size_t hb = h->channels * h->K * sample_bytes(h->dtype);
-    for (int i = 0; i < 2; ++i) {
-        SDSP_TRY(h->d_hist[i].ensure(hb), "alloc window");
-        SDSP_TRY(hipMemsetAsync(h->d_hist[i].p, 0, hb, h->stream), "zero window");
-    }
-    h->cur = 0;
-    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    SDSP_TRY(h->hist.reset(h->channels * h->K * sample_bytes(h->dtype), h->stream), "zero window");
+    return h->quiesce();
 }
 
 int pfb_create_common(sdsp_pfb** out, int dtype, const unsigned char* taps, size_t len, size_t M,
@@ -977,13 +899,11 @@ int pfb_create_common(sdsp_pfb** out, int dtype, const unsigned char* taps, size
         set_error("fewer taps than filters: sub-filter length 0");
         return SDSP_E_INVALID_ARGUMENT;
     }
-    DeviceInfo info;
-    int st = check_device(device, &info);
+    int st = check_device(device, nullptr);
     if (st) return st;
     DeviceGuard g(device);
     sdsp_pfb* h = new sdsp_pfb();
     h->dtype = dtype;
-    h->device = device;
     h->algo = default_algo() == SDSP_ALGO_FMA ? SDSP_ALGO_FMA : SDSP_ALGO_EXACT;  // (EXACT / FMA only)
     h->M = M;
     h->K = K;
@@ -994,7 +914,7 @@ int pfb_create_common(sdsp_pfb** out, int dtype, const unsigned char* taps, size
     for (size_t p = 0; p < M; ++p)
         for (size_t idx = 0; idx < K; ++idx)
             std::memcpy(&h->cb[(p * K + (K - idx - 1)) * cbytes], taps + (p + idx * M) * cbytes, cbytes);
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    hipError_t e = h->open(device);
     if (e == hipSuccess) e = h->d_cb.ensure(h->cb.size());
     if (e == hipSuccess) e = hipMemcpy(h->d_cb.p, h->cb.data(), h->cb.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -1056,43 +976,26 @@ int sdsp_interp_create(sdsp_pfb** out, int dtype, const void* taps, size_t len, 
     return pfb_create_common(out, dtype, eff.data(), K * M, M, one.data(), true, device);
 }
 
-void sdsp_pfb_destroy(sdsp_pfb* h) {
-    if (!h) return;
-    {
-        DeviceGuard g(h->device);
-        if (h->stream) {
-            (void)hipStreamSynchronize(h->stream);
-            (void)hipStreamDestroy(h->stream);
-        }
-        h->d_cb.release();
-        h->d_hist[0].release();
-        h->d_hist[1].release();
-        h->stage_in.release();
-        h->stage_out.release();
-    }
-    delete h;
-}
+void sdsp_pfb_destroy(sdsp_pfb* h) { destroy_handle(h); }
 
 int sdsp_pfb_clone(const sdsp_pfb* h, sdsp_pfb** out) {
     if (!h || !out) return SDSP_E_INVALID_ARGUMENT;
-    DeviceInfo info;
-    int st = check_device(h->device, &info);
+    int st = check_device(h->device, nullptr);
     if (st) return st;
     DeviceGuard g(h->device);
     sdsp_pfb* c = new sdsp_pfb();
-    c->dtype = h->dtype; c->device = h->device; c->M = h->M; c->K = h->K; c->channels = h->channels;
+    c->dtype = h->dtype; c->M = h->M; c->K = h->K; c->channels = h->channels;
     c->interp = h->interp; c->cb = h->cb; c->scale = h->scale; c->algo = h->algo;
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    hipError_t e = c->open(h->device);
     if (e == hipSuccess) e = c->d_cb.ensure(c->cb.size());
     if (e == hipSuccess) e = hipMemcpy(c->d_cb.p, c->cb.data(), c->cb.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { st = device_status(e, "pfb clone"); sdsp_pfb_destroy(c); return st; }
     st = pfb_alloc_state(c);
     if (st) { sdsp_pfb_destroy(c); return st; }
     const size_t hb = h->channels * h->K * sample_bytes(h->dtype);
-    e = h->fence.wait();
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipMemcpy(c->d_hist[0].p, h->d_hist[h->cur].p, hb, hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) { st = device_status(e, "pfb clone state"); sdsp_pfb_destroy(c); return st; }
+    st = h->quiesce();
+    if (!st) st = device_status(hipMemcpy(c->hist.front(), h->hist.front(), hb, hipMemcpyDeviceToDevice), "pfb clone state");
+    if (st) { sdsp_pfb_destroy(c); return st; }
     *out = c;
     return SDSP_OK;
 }
@@ -1140,13 +1043,13 @@ int sdsp_pfb_execute_block_device(sdsp_pfb* h, const void* d_in, size_t n, void*
     }
     // work queued on another stream (the fence) reads or writes the window this launch uses
     SDSP_TRY(h->fence.order_before(s), "order after queued work");
-    PfbArgs a{d_in, h->d_hist[h->cur].p, h->d_cb.p, d_out, n, h->channels, (int)h->K, (int)h->M, (int)h->K,
+    PfbArgs a{d_in, h->hist.front(), h->d_cb.p, d_out, n, h->channels, (int)h->K, (int)h->M, (int)h->K,
               h->algo != SDSP_ALGO_FMA};
     SDSP_TRY(launch_pfb(h->dtype, a, s), "pfb");
-    SDSP_TRY(launch_hist_update(h->dtype, d_in, h->d_hist[h->cur].p, h->d_hist[h->cur ^ 1].p, n, (int)h->K,
+    SDSP_TRY(launch_hist_update(h->dtype, d_in, h->hist.front(), h->hist.back(), n, (int)h->K,
                                 h->channels, s),
              "window update");
-    h->cur ^= 1;
+    h->hist.flip();
     SDSP_TRY(h->fence.record(s), "record fence");
     return SDSP_OK;
 }
@@ -1155,17 +1058,10 @@ int sdsp_pfb_execute_block(sdsp_pfb* h, const void* in, size_t n, void* out) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     if (n == 0) return SDSP_OK;
     DeviceGuard g(h->device);
-    SDSP_TRY(h->fence.wait(), "wait for queued work");
-    const size_t sb = sample_bytes(h->dtype);
-    SDSP_TRY(h->stage_in.ensure(h->channels * n * sb), "stage in");
-    SDSP_TRY(h->stage_out.ensure(h->channels * n * h->M * sb), "stage out");
-    SDSP_TRY(hipMemcpyAsync(h->stage_in.p, in, h->channels * n * sb, hipMemcpyHostToDevice, h->stream), "H2D");
-    int st = sdsp_pfb_execute_block_device(h, h->stage_in.p, n, h->stage_out.p, h->stream);
-    if (st) return st;
-    SDSP_TRY(hipMemcpyAsync(out, h->stage_out.p, h->channels * n * h->M * sb, hipMemcpyDeviceToHost, h->stream),
-             "D2H");
-    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    const size_t bytes = h->channels * n * sample_bytes(h->dtype);
+    return h->staged(in, bytes, out, bytes * h->M, [&](const void* d_in, void* d_out, hipStream_t s) {
+        return sdsp_pfb_execute_block_device(h, d_in, n, d_out, s);
+    });
 }
 
 int sdsp_pfb_push(sdsp_pfb* h, const void* sample) {
@@ -1175,10 +1071,10 @@ int sdsp_pfb_push(sdsp_pfb* h, const void* sample) {
     const size_t sb = sample_bytes(h->dtype);
     SDSP_TRY(h->stage_in.ensure(sb), "stage in");
     SDSP_TRY(hipMemcpyAsync(h->stage_in.p, sample, sb, hipMemcpyHostToDevice, h->stream), "H2D");
-    SDSP_TRY(launch_hist_update(h->dtype, h->stage_in.p, h->d_hist[h->cur].p, h->d_hist[h->cur ^ 1].p, 1,
+    SDSP_TRY(launch_hist_update(h->dtype, h->stage_in.p, h->hist.front(), h->hist.back(), 1,
                                 (int)h->K, 1, h->stream),
              "window push");
-    h->cur ^= 1;
+    h->hist.flip();
     SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
     return SDSP_OK;
 }
@@ -1190,7 +1086,7 @@ int sdsp_pfb_execute(sdsp_pfb* h, size_t index, void* out) {
     const size_t sb = sample_bytes(h->dtype);
     SDSP_TRY(h->stage_out.ensure(h->M * sb), "stage out");
     // all branches on the current window: x = newest sample, history = the K-1 before it
-    const unsigned char* win = (const unsigned char*)h->d_hist[h->cur].p;
+    const unsigned char* win = (const unsigned char*)h->hist.front();
     PfbArgs a{win + (h->K - 1) * sb, win, h->d_cb.p, h->stage_out.p, 1, 1, (int)h->K, (int)h->M,
               (int)h->K - 1, h->algo != SDSP_ALGO_FMA};
     SDSP_TRY(launch_pfb(h->dtype, a, h->stream), "pfb execute");
@@ -1234,8 +1130,7 @@ int sdsp_pfb_group_delay(const sdsp_pfb* h, double f, double* delay) {
 int sdsp_pfb_synchronize(sdsp_pfb* h) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     DeviceGuard g(h->device);
-    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    return h->quiesce();
 }
 
 // ===========================================================================

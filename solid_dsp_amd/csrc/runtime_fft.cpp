@@ -17,39 +17,6 @@ using namespace sdsp;
 
 namespace {
 
-#define F_TRY(expr, what)                                      \
-    do {                                                       \
-        hipError_t _e = (expr);                                \
-        if (_e != hipSuccess) return device_status(_e, what);  \
-    } while (0)
-
-struct Guard {
-    int prev = -1;
-    explicit Guard(int d) {
-        (void)hipGetDevice(&prev);
-        if (prev != d) (void)hipSetDevice(d);
-    }
-    ~Guard() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-int check_gfx950(int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) {
-        set_error("no HIP device visible (libsdsp has no CPU execution path)");
-        return SDSP_E_NO_DEVICE;
-    }
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, device) != hipSuccess || std::strncmp(p.gcnArchName, "gfx950", 6) != 0) {
-        set_error("libsdsp is built for gfx950");
-        return SDSP_E_NO_DEVICE;
-    }
-    return SDSP_OK;
-}
-
 bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 int ilog2(size_t n) {
     int l = 0;
@@ -66,12 +33,12 @@ int make_twiddles(DevBuf& buf, size_t N, bool f64) {
         w[2 * m + 1] = std::sin(a);
     }
     if (f64) {
-        F_TRY(buf.ensure(w.size() * 8), "alloc twiddles");
-        F_TRY(hipMemcpy(buf.p, w.data(), w.size() * 8, hipMemcpyHostToDevice), "copy twiddles");
+        SDSP_TRY(buf.ensure(w.size() * 8), "alloc twiddles");
+        SDSP_TRY(hipMemcpy(buf.p, w.data(), w.size() * 8, hipMemcpyHostToDevice), "copy twiddles");
     } else {
         std::vector<float> f(w.begin(), w.end());
-        F_TRY(buf.ensure(f.size() * 4), "alloc twiddles");
-        F_TRY(hipMemcpy(buf.p, f.data(), f.size() * 4, hipMemcpyHostToDevice), "copy twiddles");
+        SDSP_TRY(buf.ensure(f.size() * 4), "alloc twiddles");
+        SDSP_TRY(hipMemcpy(buf.p, f.data(), f.size() * 4, hipMemcpyHostToDevice), "copy twiddles");
     }
     return SDSP_OK;
 }
@@ -108,8 +75,8 @@ struct Pow2Plan {
             t[2048 + 2 * j] = (float)std::cos(b);
             t[2048 + 2 * j + 1] = (float)std::sin(b);
         }
-        F_TRY(twx.ensure(t.size() * 4), "alloc twiddles");
-        F_TRY(hipMemcpy(twx.p, t.data(), t.size() * 4, hipMemcpyHostToDevice), "copy twiddles");
+        SDSP_TRY(twx.ensure(t.size() * 4), "alloc twiddles");
+        SDSP_TRY(hipMemcpy(twx.p, t.data(), t.size() * 4, hipMemcpyHostToDevice), "copy twiddles");
         return SDSP_OK;
     }
     // in -> out (may alias); tmp: batch * N samples when four_step()
@@ -161,12 +128,12 @@ void host_fft_pow2(std::vector<double>& a, size_t M) {
 
 int upload(DevBuf& buf, const std::vector<double>& v, bool f64) {
     if (f64) {
-        F_TRY(buf.ensure(v.size() * 8), "alloc");
-        F_TRY(hipMemcpy(buf.p, v.data(), v.size() * 8, hipMemcpyHostToDevice), "upload");
+        SDSP_TRY(buf.ensure(v.size() * 8), "alloc");
+        SDSP_TRY(hipMemcpy(buf.p, v.data(), v.size() * 8, hipMemcpyHostToDevice), "upload");
     } else {
         std::vector<float> f(v.begin(), v.end());
-        F_TRY(buf.ensure(f.size() * 4), "alloc");
-        F_TRY(hipMemcpy(buf.p, f.data(), f.size() * 4, hipMemcpyHostToDevice), "upload");
+        SDSP_TRY(buf.ensure(f.size() * 4), "alloc");
+        SDSP_TRY(hipMemcpy(buf.p, f.data(), f.size() * 4, hipMemcpyHostToDevice), "upload");
     }
     return SDSP_OK;
 }
@@ -175,31 +142,28 @@ constexpr size_t kDirectMax = 512;  // non-power-of-two sizes up to this run the
 
 }  // namespace
 
-struct sdsp_fft {
+// (records no fence: calls on different streams share the scratch buffers unordered)
+struct sdsp_fft : HandleCore {
     size_t N = 0;
     int direction = 0;  // 0 FORWARD, 1 REVERSE
     bool f64 = true;
-    int device = 0;
     int kind = 0;       // 0 direct DFT, 1 power of two, 2 Bluestein
-    DevBuf tw, stage_in, stage_out;
+    DevBuf tw;
     Pow2Plan p2;        // kind 1: the transform; kind 2: the length-M convolution transform
     size_t M = 0;       // Bluestein convolution length (power of two >= 2N - 1)
     DevBuf chirp, spec; // Bluestein: w[N] of the direction, B[M] = FFT_M(conj chirp) / M
     DevBuf work, tmp;   // device scratch, grown with the batch
-    hipStream_t stream = nullptr;
 };
 
-struct sdsp_chan {
-    int dtype = SDSP_RC32, device = 0;
+struct sdsp_chan : HandleCore {
+    int dtype = SDSP_RC32;
     size_t M = 0, K = 0, streams = 1;
     std::vector<unsigned char> taps;
-    DevBuf cb, tw, hist[2], stage_in, stage_out;
-    int cur = 0;
+    DevBuf cb, tw;
+    PingPong hist;  // [streams][(K-1) M] oldest first
     int fast = 5;  // streaming M = 1024 kernel variant (SDSP_TUNE_CHAN_STREAMING): 8-frame rounds
     int fpb = 0;       // its frames per workgroup (SDSP_TUNE_CHAN_FRAMES_PER_BLOCK, 0 = default)
     bool xcd = true;   // XCD-contiguous chunk order (SDSP_TUNE_CHAN_XCD_ORDER)
-    hipStream_t stream = nullptr;
-    StreamFence fence;  // last caller stream an execute call was queued on
 };
 
 extern "C" {
@@ -219,15 +183,14 @@ int sdsp_fft_create(sdsp_fft** out, size_t nfft, int direction, int precision, i
         return SDSP_E_INVALID_ARGUMENT;
     }
     if (direction != 0 && direction != 1) return SDSP_E_INVALID_ARGUMENT;
-    int st = check_gfx950(device);
+    int st = check_device(device, nullptr);
     if (st) return st;
-    Guard g(device);
+    DeviceGuard g(device);
     sdsp_fft* h = new sdsp_fft();
     h->N = nfft;
     h->direction = direction;
     h->f64 = precision != 0;
-    h->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    hipError_t e = h->open(device);
     if (e != hipSuccess) { delete h; return device_status(e, "stream"); }
     if (is_pow2(nfft)) {
         h->kind = 1;
@@ -266,25 +229,7 @@ int sdsp_fft_create(sdsp_fft** out, size_t nfft, int direction, int precision, i
     return SDSP_OK;
 }
 
-void sdsp_fft_destroy(sdsp_fft* h) {
-    if (!h) return;
-    {
-        Guard g(h->device);
-        if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-        h->tw.release();
-        h->stage_in.release();
-        h->stage_out.release();
-        h->p2.tw.release();
-        h->p2.tw1.release();
-        h->p2.tw2.release();
-        h->p2.twx.release();
-        h->chirp.release();
-        h->spec.release();
-        h->work.release();
-        h->tmp.release();
-    }
-    delete h;
-}
+void sdsp_fft_destroy(sdsp_fft* h) { destroy_handle(h); }
 
 size_t sdsp_fft_len(const sdsp_fft* h) { return h ? h->N : 0; }
 
@@ -300,30 +245,30 @@ int sdsp_fft_set_tuning(sdsp_fft* h, int key, int value) {
 int sdsp_fft_execute_device(sdsp_fft* h, const void* d_in, void* d_out, size_t batch, void* stream) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     if (batch == 0) return SDSP_OK;
-    Guard g(h->device);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    DeviceGuard g(h->device);
+    hipStream_t s = pick(stream, h->stream);
     const size_t cb = h->f64 ? 16 : 8;
     const bool inv = h->direction == 1;
     if (h->kind == 0) {
         if (d_in == d_out) {  // the direct DFT reads every input per output: work from a copy
-            F_TRY(h->work.ensure(batch * h->N * cb), "dft scratch");
-            F_TRY(hipMemcpyAsync(h->work.p, d_in, batch * h->N * cb, hipMemcpyDeviceToDevice, s), "dft copy");
+            SDSP_TRY(h->work.ensure(batch * h->N * cb), "dft scratch");
+            SDSP_TRY(hipMemcpyAsync(h->work.p, d_in, batch * h->N * cb, hipMemcpyDeviceToDevice, s), "dft copy");
             d_in = h->work.p;
         }
         FftArgs a{d_in, d_out, h->tw.p, (int)h->N, ilog2(h->N), false, inv, batch};
-        F_TRY(launch_fft(h->f64, a, s), "fft");
+        SDSP_TRY(launch_fft(h->f64, a, s), "fft");
     } else if (h->kind == 1) {
-        if (h->p2.four_step()) F_TRY(h->tmp.ensure(batch * h->N * cb), "fft scratch");
-        F_TRY(h->p2.run(h->f64, d_in, d_out, h->tmp.p, batch, inv, s), "fft");
+        if (h->p2.four_step()) SDSP_TRY(h->tmp.ensure(batch * h->N * cb), "fft scratch");
+        SDSP_TRY(h->p2.run(h->f64, d_in, d_out, h->tmp.p, batch, inv, s), "fft");
     } else {
         const long long N = (long long)h->N, M = (long long)h->M;
-        F_TRY(h->work.ensure(batch * h->M * cb), "bluestein scratch");
-        if (h->p2.four_step()) F_TRY(h->tmp.ensure(batch * h->M * cb), "bluestein scratch");
-        F_TRY(launch_bluestein(h->f64, 0, d_in, h->work.p, h->chirp.p, N, M, (long long)batch, s), "bluestein in");
-        F_TRY(h->p2.run(h->f64, h->work.p, h->work.p, h->tmp.p, batch, false, s), "bluestein fft");
-        F_TRY(launch_bluestein(h->f64, 1, nullptr, h->work.p, h->spec.p, N, M, (long long)batch, s), "bluestein mul");
-        F_TRY(h->p2.run(h->f64, h->work.p, h->work.p, h->tmp.p, batch, true, s), "bluestein ifft");
-        F_TRY(launch_bluestein(h->f64, 2, h->work.p, d_out, h->chirp.p, N, M, (long long)batch, s), "bluestein out");
+        SDSP_TRY(h->work.ensure(batch * h->M * cb), "bluestein scratch");
+        if (h->p2.four_step()) SDSP_TRY(h->tmp.ensure(batch * h->M * cb), "bluestein scratch");
+        SDSP_TRY(launch_bluestein(h->f64, 0, d_in, h->work.p, h->chirp.p, N, M, (long long)batch, s), "bluestein in");
+        SDSP_TRY(h->p2.run(h->f64, h->work.p, h->work.p, h->tmp.p, batch, false, s), "bluestein fft");
+        SDSP_TRY(launch_bluestein(h->f64, 1, nullptr, h->work.p, h->spec.p, N, M, (long long)batch, s), "bluestein mul");
+        SDSP_TRY(h->p2.run(h->f64, h->work.p, h->work.p, h->tmp.p, batch, true, s), "bluestein ifft");
+        SDSP_TRY(launch_bluestein(h->f64, 2, h->work.p, d_out, h->chirp.p, N, M, (long long)batch, s), "bluestein out");
     }
     return SDSP_OK;
 }
@@ -339,16 +284,11 @@ int sdsp_fft_method(const sdsp_fft* h) {
 int sdsp_fft_execute(sdsp_fft* h, const void* in, void* out, size_t batch) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     if (batch == 0) return SDSP_OK;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     const size_t bytes = h->N * batch * (h->f64 ? 16 : 8);
-    F_TRY(h->stage_in.ensure(bytes), "stage");
-    F_TRY(h->stage_out.ensure(bytes), "stage");
-    F_TRY(hipMemcpyAsync(h->stage_in.p, in, bytes, hipMemcpyHostToDevice, h->stream), "H2D");
-    int st = sdsp_fft_execute_device(h, h->stage_in.p, h->stage_out.p, batch, h->stream);
-    if (st) return st;
-    F_TRY(hipMemcpyAsync(out, h->stage_out.p, bytes, hipMemcpyDeviceToHost, h->stream), "D2H");
-    F_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    return h->staged(in, bytes, out, bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
+        return sdsp_fft_execute_device(h, d_in, d_out, batch, s);
+    });
 }
 
 // ---- channeliser -----------------------------------------------------------
@@ -367,12 +307,11 @@ int sdsp_chan_create(sdsp_chan** out, int dtype, const void* taps, size_t len, s
     }
     const size_t K = len / M;
     if (K == 0) { set_error("fewer taps than channels"); return SDSP_E_INVALID_ARGUMENT; }
-    int st = check_gfx950(device);
+    int st = check_device(device, nullptr);
     if (st) return st;
-    Guard g(device);
+    DeviceGuard g(device);
     sdsp_chan* h = new sdsp_chan();
     h->dtype = dtype;
-    h->device = device;
     h->M = M;
     h->K = K;
     const size_t cbytes = coef_bytes(dtype);
@@ -382,7 +321,7 @@ int sdsp_chan_create(sdsp_chan** out, int dtype, const void* taps, size_t len, s
     for (size_t p = 0; p < M; ++p)
         for (size_t idx = 0; idx < K; ++idx)
             std::memcpy(&cb[(p * K + (K - 1 - idx)) * cbytes], &h->taps[(p + idx * M) * cbytes], cbytes);
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    hipError_t e = h->open(device);
     if (e == hipSuccess) e = h->cb.ensure(cb.size());
     if (e == hipSuccess) e = hipMemcpy(h->cb.p, cb.data(), cb.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { st = device_status(e, "chan create"); sdsp_chan_destroy(h); return st; }
@@ -393,31 +332,15 @@ int sdsp_chan_create(sdsp_chan** out, int dtype, const void* taps, size_t len, s
     return SDSP_OK;
 }
 
-void sdsp_chan_destroy(sdsp_chan* h) {
-    if (!h) return;
-    {
-        Guard g(h->device);
-        (void)h->fence.wait();
-        if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-        h->cb.release(); h->tw.release(); h->hist[0].release(); h->hist[1].release();
-        h->stage_in.release(); h->stage_out.release();
-    }
-    delete h;
-}
+void sdsp_chan_destroy(sdsp_chan* h) { destroy_handle(h); }
 
 int sdsp_chan_set_streams(sdsp_chan* h, size_t streams) {
     if (!h || streams == 0) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
-    F_TRY(h->fence.wait(), "wait for queued work");  // a queued block may still read the history
+    DeviceGuard g(h->device);
+    SDSP_TRY(h->fence.wait(), "wait for queued work");  // a queued block may still read the history
     h->streams = streams;
-    const size_t hb = streams * (h->K - 1) * h->M * sample_bytes(h->dtype);
-    for (int i = 0; i < 2; ++i) {
-        F_TRY(h->hist[i].ensure(hb), "alloc history");
-        if (hb) F_TRY(hipMemsetAsync(h->hist[i].p, 0, hb, h->stream), "zero history");
-    }
-    h->cur = 0;
-    F_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    SDSP_TRY(h->hist.reset(streams * (h->K - 1) * h->M * sample_bytes(h->dtype), h->stream), "zero history");
+    return h->quiesce();
 }
 
 int sdsp_chan_set_tuning(sdsp_chan* h, int key, int value) {
@@ -446,25 +369,25 @@ int sdsp_chan_execute_block_device(sdsp_chan* h, const void* d_in, size_t n, voi
         set_error("input and output blocks overlap (in-place channelising is not supported)");
         return SDSP_E_INVALID_ARGUMENT;
     }
-    Guard g(h->device);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    F_TRY(h->fence.order_before(s), "order after queued work");  // the history this launch reads
-    ChanArgs a{d_in, h->hist[h->cur].p, h->cb.p, d_out, h->tw.p, (int)h->M, ilog2(h->M), (int)h->K, n, fr, h->streams};
+    DeviceGuard g(h->device);
+    hipStream_t s = pick(stream, h->stream);
+    SDSP_TRY(h->fence.order_before(s), "order after queued work");  // the history this launch reads
+    ChanArgs a{d_in, h->hist.front(), h->cb.p, d_out, h->tw.p, (int)h->M, ilog2(h->M), (int)h->K, n, fr, h->streams};
     a.fast = h->fast;
     a.frames_per_block = h->fpb;
     a.xcd_order = h->xcd;
-    F_TRY(launch_chan(h->dtype == SDSP_RC64, a, s), "channeliser");
+    SDSP_TRY(launch_chan(h->dtype == SDSP_RC64, a, s), "channeliser");
     const int H = (int)((h->K - 1) * h->M);
-    F_TRY(launch_hist_update(h->dtype, d_in, h->hist[h->cur].p, h->hist[h->cur ^ 1].p, n, H, h->streams, s),
+    SDSP_TRY(launch_hist_update(h->dtype, d_in, h->hist.front(), h->hist.back(), n, H, h->streams, s),
           "history update");
-    h->cur ^= 1;
-    F_TRY(h->fence.record(s), "record fence");
+    h->hist.flip();
+    SDSP_TRY(h->fence.record(s), "record fence");
     return SDSP_OK;
 }
 
 int sdsp_chan_execute_block(sdsp_chan* h, const void* in, size_t n, void* out, size_t* frames) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     const size_t bytes = h->streams * n * sample_bytes(h->dtype);
     if (n % h->M) {
         set_error("channeliser blocks must be a whole number of M-sample frames");
@@ -472,22 +395,15 @@ int sdsp_chan_execute_block(sdsp_chan* h, const void* in, size_t n, void* out, s
     }
     if (frames) *frames = n / h->M;
     if (n == 0) return SDSP_OK;
-    F_TRY(h->stage_in.ensure(bytes), "stage");
-    F_TRY(h->stage_out.ensure(bytes), "stage");
-    F_TRY(hipMemcpyAsync(h->stage_in.p, in, bytes, hipMemcpyHostToDevice, h->stream), "H2D");
-    int st = sdsp_chan_execute_block_device(h, h->stage_in.p, n, h->stage_out.p, nullptr, h->stream);
-    if (st) return st;
-    F_TRY(hipMemcpyAsync(out, h->stage_out.p, bytes, hipMemcpyDeviceToHost, h->stream), "D2H");
-    F_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    return h->staged(in, bytes, out, bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
+        return sdsp_chan_execute_block_device(h, d_in, n, d_out, nullptr, s);
+    });
 }
 
 int sdsp_chan_synchronize(sdsp_chan* h) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
-    F_TRY(h->fence.wait(), "wait for queued work");
-    F_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    DeviceGuard g(h->device);
+    return h->quiesce();
 }
 
 // ---- DotProduct ---------------------------------------------------------------
@@ -498,8 +414,8 @@ int sdsp_dot_execute_batched_device(int dtype, const void* coefs, size_t len, in
     if (dtype < 0 || dtype > 5 || direction < 0 || direction > 1) return SDSP_E_INVALID_ARGUMENT;
     if (batch == 0) return SDSP_OK;
     int dev = 0;
-    F_TRY(hipGetDevice(&dev), "device");
-    int st = check_gfx950(dev);
+    SDSP_TRY(hipGetDevice(&dev), "device");
+    int st = check_device(dev, nullptr);
     if (st) return st;
     const size_t cb = coef_bytes(dtype);
     std::vector<unsigned char> c((const unsigned char*)coefs, (const unsigned char*)coefs + len * cb);
@@ -507,12 +423,12 @@ int sdsp_dot_execute_batched_device(int dtype, const void* coefs, size_t len, in
         for (size_t i = 0; i < len / 2; ++i)
             std::swap_ranges(&c[i * cb], &c[i * cb] + cb, &c[(len - 1 - i) * cb]);
     DevBuf d_c;
-    F_TRY(d_c.ensure(c.size()), "alloc coefs");
+    SDSP_TRY(d_c.ensure(c.size()), "alloc coefs");
     hipStream_t s = (hipStream_t)stream;
-    F_TRY(hipMemcpyAsync(d_c.p, c.data(), c.size(), hipMemcpyHostToDevice, s), "copy coefs");
+    SDSP_TRY(hipMemcpyAsync(d_c.p, c.data(), c.size(), hipMemcpyHostToDevice, s), "copy coefs");
     DotArgs a{d_c.p, (int)std::min(n, len), d_samples, stride, batch, d_out};
-    F_TRY(launch_dot(dtype, a, s), "dot");
-    F_TRY(hipStreamSynchronize(s), "sync");  // d_c is released on return
+    SDSP_TRY(launch_dot(dtype, a, s), "dot");
+    SDSP_TRY(hipStreamSynchronize(s), "sync");  // d_c is released on return
     return SDSP_OK;
 }
 
@@ -521,17 +437,17 @@ int sdsp_dot_execute(int dtype, const void* coefs, size_t len, int direction, co
                      void* out) {
     if (dtype < 0 || dtype > 5) return SDSP_E_INVALID_ARGUMENT;
     int dev = 0;
-    F_TRY(hipGetDevice(&dev), "device");
-    int st = check_gfx950(dev);
+    SDSP_TRY(hipGetDevice(&dev), "device");
+    int st = check_device(dev, nullptr);
     if (st) return st;
     const size_t sb = sample_bytes(dtype);
     DevBuf s, o;
-    F_TRY(s.ensure(std::max<size_t>(n, 1) * sb), "alloc");
-    F_TRY(o.ensure(sb), "alloc");
-    if (n) F_TRY(hipMemcpy(s.p, samples, n * sb, hipMemcpyHostToDevice), "H2D");
+    SDSP_TRY(s.ensure(std::max<size_t>(n, 1) * sb), "alloc");
+    SDSP_TRY(o.ensure(sb), "alloc");
+    if (n) SDSP_TRY(hipMemcpy(s.p, samples, n * sb, hipMemcpyHostToDevice), "H2D");
     st = sdsp_dot_execute_batched_device(dtype, coefs, len, direction, s.p, n, n, 1, o.p, nullptr);
     if (st) return st;
-    F_TRY(hipMemcpy(out, o.p, sb, hipMemcpyDeviceToHost), "D2H");
+    SDSP_TRY(hipMemcpy(out, o.p, sb, hipMemcpyDeviceToHost), "D2H");
     return SDSP_OK;
 }
 

@@ -20,12 +20,6 @@ using namespace sdsp;
 
 namespace {
 
-#define IIR_TRY(expr, what)                                    \
-    do {                                                       \
-        hipError_t _e = (expr);                                \
-        if (_e != hipSuccess) return device_status(_e, what);  \
-    } while (0)
-
 constexpr int kMaxGroupSections = 8;  // sections per kernel launch (longer cascades chain launches)
 constexpr int kScanLanes = 256;
 constexpr int kMaxNormalCap = 32;
@@ -47,19 +41,6 @@ struct Group {
     std::vector<double> wc64;
     std::vector<double> wscale;  // [2 count]: reference state = kernel state * wscale
     DevBuf d_wcoefs;
-};
-
-struct DeviceGuardI {
-    int prev = -1;
-    explicit DeviceGuardI(int d) {
-        (void)hipGetDevice(&prev);
-        if (prev != d) (void)hipSetDevice(d);
-    }
-    ~DeviceGuardI() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
 };
 
 using Mat = std::vector<double>;  // row-major D x D
@@ -95,8 +76,8 @@ double norm_inf(const Mat& a, int D) {
 
 }  // namespace
 
-struct sdsp_iir {
-    int dtype = 0, device = 0, cus = 256;
+struct sdsp_iir : HandleCore {
+    int dtype = 0, cus = 256;
     int type = 1;       // 0 Normal, 1 SecondOrder
     int mode = 0;       // 0 IIRFilter, 1 DecimatingIIRFilter, 2 InterpolatingIIRFilter
     size_t M = 1;
@@ -107,13 +88,10 @@ struct sdsp_iir {
     std::vector<unsigned char> cdev;     // normalised coefficients in the Coef type (device layout)
     int S = 0, nb = 0, na = 0, cap = 0;
     std::vector<Group> groups;
-    DevBuf d_coefs, d_coefs_nrm, d_state[2], d_tmp[2], d_carry[2];
-    int cur = 0;
+    DevBuf d_coefs, d_coefs_nrm, d_tmp[2], d_carry[2];
+    PingPong state;
     int algo = SDSP_ALGO_EXACT;  // reference-order recurrence unless the caller opts in (sdsp.h)
     int wscan = 1;  // 0: block scan; 1-6: wave-scan variant 0-5 (kern_iir_wscan.hip; sdsp_iir_set_tuning)
-    hipStream_t stream = nullptr;
-    mutable StreamFence fence;  // last caller stream an execute call was queued on
-    DevBuf stage_in, stage_out;
     size_t state_per_ch() const { return type == 1 ? (size_t)(2 * S) : (size_t)(cap - 1); }
 };
 
@@ -137,18 +115,11 @@ void push_coef(std::vector<unsigned char>& out, double v, int dt) {
 }
 
 int iir_alloc_state(sdsp_iir* h) {
-    IIR_TRY(h->fence.wait(), "wait for queued work");
-    const size_t sb = sample_bytes(h->dtype) * h->channels * h->state_per_ch();
-    for (int i = 0; i < 2; ++i) {
-        IIR_TRY(h->d_state[i].ensure(sb), "alloc state");
-        if (sb) IIR_TRY(hipMemsetAsync(h->d_state[i].p, 0, sb, h->stream), "zero state");
-    }
-    h->cur = 0;
+    SDSP_TRY(h->fence.wait(), "wait for queued work");
+    SDSP_TRY(h->state.reset(sample_bytes(h->dtype) * h->channels * h->state_per_ch(), h->stream), "zero state");
     h->phase = 0;
-    IIR_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    return h->quiesce();
 }
-
 
 // state dimension of a scanned group: the SOS sections' (w1, w2) pairs, or the
 // Normal DF-II delay line (cap - 1 values)
@@ -315,8 +286,8 @@ int scan_tables(const sdsp_iir* h, const Group& g, bool scaled, int B, int max_w
             At = matmul(At, A64, D);
         }
         if (!carry_well_conditioned(h, g, cf, B, AB)) return SDSP_OK;
-        IIR_TRY(dPhi->ensure(Phi.size()), "alloc Phi");
-        IIR_TRY(hipMemcpy(dPhi->p, Phi.data(), Phi.size(), hipMemcpyHostToDevice), "copy Phi");
+        SDSP_TRY(dPhi->ensure(Phi.size()), "alloc Phi");
+        SDSP_TRY(hipMemcpy(dPhi->p, Phi.data(), Phi.size(), hipMemcpyHostToDevice), "copy Phi");
         *exact = true;
     }
     std::vector<unsigned char> P;
@@ -325,8 +296,8 @@ int scan_tables(const sdsp_iir* h, const Group& g, bool scaled, int B, int max_w
         for (double v : Pk) push_coef(P, v, h->dtype);
         Pk = matmul(Pk, Pk, D);
     }
-    IIR_TRY(dP->ensure(P.size()), "alloc P");
-    IIR_TRY(hipMemcpy(dP->p, P.data(), P.size(), hipMemcpyHostToDevice), "copy P");
+    SDSP_TRY(dP->ensure(P.size()), "alloc P");
+    SDSP_TRY(hipMemcpy(dP->p, P.data(), P.size(), hipMemcpyHostToDevice), "copy P");
     if (!dCr) return SDSP_OK;
     std::vector<double> resp((size_t)B * D);
     for (int d = 0; d < D; ++d) {  // output response to basis state e_d, zero input
@@ -343,8 +314,8 @@ int scan_tables(const sdsp_iir* h, const Group& g, bool scaled, int B, int max_w
     } else {
         for (double v : resp) push_coef(Cr, v, h->dtype);
     }
-    IIR_TRY(dCr->ensure(Cr.size()), "alloc Cr");
-    IIR_TRY(hipMemcpy(dCr->p, Cr.data(), Cr.size(), hipMemcpyHostToDevice), "copy Cr");
+    SDSP_TRY(dCr->ensure(Cr.size()), "alloc Cr");
+    SDSP_TRY(hipMemcpy(dCr->p, Cr.data(), Cr.size(), hipMemcpyHostToDevice), "copy Cr");
     return SDSP_OK;
 }
 
@@ -435,8 +406,8 @@ int plan_groups(sdsp_iir* h) {
         std::vector<unsigned char> c;
         for (int i = 0; i <= D; ++i) push_coef(c, i < h->nb ? h->c64[i] : 0.0, h->dtype);
         for (int i = 0; i < D; ++i) push_coef(c, i < h->na - 1 ? h->c64[h->nb + i] : 0.0, h->dtype);
-        IIR_TRY(h->d_coefs_nrm.ensure(c.size()), "alloc normal coefs");
-        IIR_TRY(hipMemcpy(h->d_coefs_nrm.p, c.data(), c.size(), hipMemcpyHostToDevice), "copy normal coefs");
+        SDSP_TRY(h->d_coefs_nrm.ensure(c.size()), "alloc normal coefs");
+        SDSP_TRY(hipMemcpy(h->d_coefs_nrm.p, c.data(), c.size(), hipMemcpyHostToDevice), "copy normal coefs");
         return SDSP_OK;
     }
     if (h->type != 1) return SDSP_OK;
@@ -465,8 +436,8 @@ int plan_groups(sdsp_iir* h) {
         for (double v : g.wc64) push_coef(c, v, h->dtype);
         for (double v : g.wscale) push_coef(c, v, h->dtype);
         for (double v : g.wscale) push_coef(c, 1.0 / v, h->dtype);
-        IIR_TRY(g.d_wcoefs.ensure(c.size()), "alloc wave-scan coefs");
-        IIR_TRY(hipMemcpy(g.d_wcoefs.p, c.data(), c.size(), hipMemcpyHostToDevice), "copy wave-scan coefs");
+        SDSP_TRY(g.d_wcoefs.ensure(c.size()), "alloc wave-scan coefs");
+        SDSP_TRY(hipMemcpy(g.d_wcoefs.p, c.data(), c.size(), hipMemcpyHostToDevice), "copy wave-scan coefs");
     }
     return SDSP_OK;
 }
@@ -508,7 +479,6 @@ int iir_create(sdsp_iir** out, int dtype, const void* ff, size_t nff, const void
     const size_t cb = coef_bytes(dtype);
     sdsp_iir* h = new sdsp_iir();
     h->dtype = dtype;
-    h->device = device;
     h->algo = default_algo();
     h->type = type;
     // real f32: 128-byte chunks (B = 32; cfg3 1.75 -> 1.72 ms, its compute-only ablation 1.63 ->
@@ -540,21 +510,13 @@ int iir_create(sdsp_iir** out, int dtype, const void* ff, size_t nff, const void
         for (size_t i = 0; i < nff; ++i) { const double v = cdiv_t(cval(h->ff, dtype, i), a0, dtype); h->c64.push_back(v); push_coef(h->cdev, v, dtype); }
         for (size_t i = 1; i < nfb; ++i) { const double v = cdiv_t(cval(h->fb, dtype, i), a0, dtype); h->c64.push_back(v); push_coef(h->cdev, v, dtype); }
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+    st = check_device(device, &h->cus);
+    if (st) {
         delete h;
-        set_error("no HIP device visible (libsdsp has no CPU execution path)");
-        return SDSP_E_NO_DEVICE;
+        return st;
     }
-    DeviceGuardI g(device);
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, device) != hipSuccess || std::strncmp(p.gcnArchName, "gfx950", 6) != 0) {
-        delete h;
-        set_error("libsdsp is built for gfx950");
-        return SDSP_E_NO_DEVICE;
-    }
-    h->cus = p.multiProcessorCount;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    DeviceGuard g(device);
+    hipError_t e = h->open(device);
     if (e == hipSuccess) e = h->d_coefs.ensure(h->cdev.size());
     if (e == hipSuccess) e = hipMemcpy(h->d_coefs.p, h->cdev.data(), h->cdev.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -622,28 +584,7 @@ int sdsp_sos_create(sdsp_iir** out, const double* ff, size_t nff, const double* 
     return iir_create(out, SDSP_RR64, ff, 3, fb, 3, 1, 0, 1, device);
 }
 
-void sdsp_iir_destroy(sdsp_iir* h) {
-    if (!h) return;
-    {
-        DeviceGuardI g(h->device);
-        (void)h->fence.wait();
-        if (h->stream) {
-            (void)hipStreamSynchronize(h->stream);
-            (void)hipStreamDestroy(h->stream);
-        }
-        h->d_coefs.release();
-        h->d_coefs_nrm.release();
-        for (int i = 0; i < 2; ++i) { h->d_state[i].release(); h->d_tmp[i].release(); h->d_carry[i].release(); }
-        for (auto& g : h->groups) {
-            g.d_P.release();
-            g.d_wcoefs.release();
-            for (auto& w : g.ws) { w.d_P.release(); w.d_Cr.release(); w.d_Phi.release(); }
-        }
-        h->stage_in.release();
-        h->stage_out.release();
-    }
-    delete h;
-}
+void sdsp_iir_destroy(sdsp_iir* h) { destroy_handle(h); }
 
 int sdsp_iir_clone(const sdsp_iir* h, sdsp_iir** out) {
     if (!h || !out) return SDSP_E_INVALID_ARGUMENT;
@@ -652,25 +593,24 @@ int sdsp_iir_clone(const sdsp_iir* h, sdsp_iir** out) {
                         h->mode, h->M, h->device);
     if (st) return st;
     sdsp_iir* c = *out;
-    DeviceGuardI g(h->device);
+    DeviceGuard g(h->device);
     c->algo = h->algo;
     c->wscan = h->wscan;
     if (h->channels != 1) {
         st = sdsp_iir_set_channels(c, h->channels);
         if (st) return st;
     }
-    IIR_TRY(h->fence.wait(), "wait for queued work");
-    IIR_TRY(hipStreamSynchronize(h->stream), "sync");
+    st = h->quiesce();
+    if (st) return st;
     const size_t sb = sample_bytes(h->dtype) * h->channels * h->state_per_ch();
-    if (sb) IIR_TRY(hipMemcpy(c->d_state[0].p, h->d_state[h->cur].p, sb, hipMemcpyDeviceToDevice), "clone state");
-    c->cur = 0;
+    if (sb) SDSP_TRY(hipMemcpy(c->state.front(), h->state.front(), sb, hipMemcpyDeviceToDevice), "clone state");
     c->phase = h->phase;
     return SDSP_OK;
 }
 
 int sdsp_iir_set_channels(sdsp_iir* h, size_t channels) {
     if (!h || channels == 0) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuardI g(h->device);
+    DeviceGuard g(h->device);
     h->channels = channels;
     return iir_alloc_state(h);
 }
@@ -715,8 +655,8 @@ size_t sdsp_iir_output_count(const sdsp_iir* h, size_t n) {
 
 int sdsp_iir_execute_block_device(sdsp_iir* h, const void* d_in, size_t n, void* d_out, size_t* n_out, void* stream) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuardI g(h->device);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    DeviceGuard g(h->device);
+    hipStream_t s = pick(stream, h->stream);
     const size_t nout = sdsp_iir_output_count(h, n);
     if (n_out) *n_out = nout;
     if (n == 0) return SDSP_OK;
@@ -726,13 +666,13 @@ int sdsp_iir_execute_block_device(sdsp_iir* h, const void* d_in, size_t n, void*
         return SDSP_E_INVALID_ARGUMENT;
     }
     // work queued on another stream (the fence) reads or writes the state this launch uses
-    IIR_TRY(h->fence.order_before(s), "order after queued work");
+    SDSP_TRY(h->fence.order_before(s), "order after queued work");
     const int Mi = h->mode == 2 ? (int)h->M : 1;
     const int Md = h->mode == 1 ? (int)h->M : 1;
     const size_t nd = n * Mi;
     const size_t sbytes = sample_bytes(h->dtype);
-    unsigned char* st_in = (unsigned char*)h->d_state[h->cur].p;
-    unsigned char* st_out = (unsigned char*)h->d_state[h->cur ^ 1].p;
+    unsigned char* st_in = (unsigned char*)h->state.front();
+    unsigned char* st_out = (unsigned char*)h->state.back();
     const size_t cb = coef_bytes(h->dtype);
     if (h->type == 0) {
         IirArgs a{d_in, d_out, h->d_coefs.p, nullptr, st_in, st_out, n, nout, h->channels, 0, h->nb, h->na, h->cap,
@@ -755,22 +695,22 @@ int sdsp_iir_execute_block_device(sdsp_iir* h, const void* d_in, size_t n, void*
                 if (b.wc == 0) {
                     b.Phi = gr.ws[wv].d_Phi.p;
                     const size_t bytes = h->channels * W * (size_t)(h->cap - 1) * sbytes;
-                    IIR_TRY(h->d_carry[0].ensure(bytes), "iir carry scratch");
-                    IIR_TRY(h->d_carry[1].ensure(bytes), "iir carry scratch");
+                    SDSP_TRY(h->d_carry[0].ensure(bytes), "iir carry scratch");
+                    SDSP_TRY(h->d_carry[1].ensure(bytes), "iir carry scratch");
                     b.G = h->d_carry[0].p;
                     b.Cin = h->d_carry[1].p;
                     b.scratch_waves = W;
                 }
-                IIR_TRY(launch_iir_wscan(h->dtype, b, s), "iir normal wave scan");
+                SDSP_TRY(launch_iir_wscan(h->dtype, b, s), "iir normal wave scan");
                 scanned = true;
             }
         }
-        if (!scanned) IIR_TRY(launch_iir(h->dtype, a, s), "iir normal");
+        if (!scanned) SDSP_TRY(launch_iir(h->dtype, a, s), "iir normal");
     } else {
         const size_t ng = h->groups.size();
         if (ng > 1) {
-            IIR_TRY(h->d_tmp[0].ensure(nd * h->channels * sbytes), "iir tmp");
-            IIR_TRY(h->d_tmp[1].ensure(nd * h->channels * sbytes), "iir tmp");
+            SDSP_TRY(h->d_tmp[0].ensure(nd * h->channels * sbytes), "iir tmp");
+            SDSP_TRY(h->d_tmp[1].ensure(nd * h->channels * sbytes), "iir tmp");
         }
         size_t soff = 0;
         const void* src = d_in;
@@ -803,44 +743,40 @@ int sdsp_iir_execute_block_device(sdsp_iir* h, const void* d_in, size_t n, void*
                     a.Phi = gr.ws[wv].d_Phi.p;
                     const size_t W = iir_wscan_waves(h->dtype, a);
                     const size_t bytes = h->channels * W * 2 * gr.count * sbytes;
-                    IIR_TRY(h->d_carry[0].ensure(bytes), "iir carry scratch");
-                    IIR_TRY(h->d_carry[1].ensure(bytes), "iir carry scratch");
+                    SDSP_TRY(h->d_carry[0].ensure(bytes), "iir carry scratch");
+                    SDSP_TRY(h->d_carry[1].ensure(bytes), "iir carry scratch");
                     a.G = h->d_carry[0].p;
                     a.Cin = h->d_carry[1].p;
                     a.scratch_waves = W;
                 }
-                IIR_TRY(launch_iir_wscan(h->dtype, a, s), "iir sos wave scan");
+                SDSP_TRY(launch_iir_wscan(h->dtype, a, s), "iir sos wave scan");
             } else if (a.algo_scan && (gr.wc == 0 || wv >= 0)) {  // block scan needs the decaying response;
                 a.algo_scan = false;                             // an unbounded carry chain runs serial
-                IIR_TRY(launch_iir(h->dtype, a, s), "iir sos");
+                SDSP_TRY(launch_iir(h->dtype, a, s), "iir sos");
             } else {
-                IIR_TRY(launch_iir(h->dtype, a, s), "iir sos");
+                SDSP_TRY(launch_iir(h->dtype, a, s), "iir sos");
             }
             soff += h->channels * 2 * gr.count * sbytes;
             src = dst;
         }
     }
-    h->cur ^= 1;
+    h->state.flip();
     if (h->mode == 1) h->phase = (h->phase + nd) % h->M;
-    IIR_TRY(h->fence.record(s), "record fence");
+    SDSP_TRY(h->fence.record(s), "record fence");
     return SDSP_OK;
 }
 
 int sdsp_iir_execute_block(sdsp_iir* h, const void* in, size_t n, void* out, size_t* n_out) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuardI g(h->device);
+    DeviceGuard g(h->device);
     const size_t sb = sample_bytes(h->dtype);
     const size_t nout = sdsp_iir_output_count(h, n);
     if (n_out) *n_out = nout;
     if (n == 0) return SDSP_OK;
-    IIR_TRY(h->stage_in.ensure(h->channels * n * sb), "stage in");
-    IIR_TRY(h->stage_out.ensure(h->channels * std::max<size_t>(nout, 1) * sb), "stage out");
-    IIR_TRY(hipMemcpyAsync(h->stage_in.p, in, h->channels * n * sb, hipMemcpyHostToDevice, h->stream), "H2D");
-    int st = sdsp_iir_execute_block_device(h, h->stage_in.p, n, h->stage_out.p, nullptr, h->stream);
-    if (st) return st;
-    if (nout) IIR_TRY(hipMemcpyAsync(out, h->stage_out.p, h->channels * nout * sb, hipMemcpyDeviceToHost, h->stream), "D2H");
-    IIR_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    return h->staged(in, h->channels * n * sb, out, h->channels * nout * sb,
+                     [&](const void* d_in, void* d_out, hipStream_t s) {
+                         return sdsp_iir_execute_block_device(h, d_in, n, d_out, nullptr, s);
+                     });
 }
 
 int sdsp_iir_execute(sdsp_iir* h, const void* sample, void* out, size_t* n_out) {
@@ -850,7 +786,7 @@ int sdsp_iir_execute(sdsp_iir* h, const void* sample, void* out, size_t* n_out) 
 
 int sdsp_iir_reset(sdsp_iir* h) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuardI g(h->device);
+    DeviceGuard g(h->device);
     return iir_alloc_state(h);
 }
 
@@ -858,22 +794,20 @@ size_t sdsp_iir_state_len(const sdsp_iir* h) { return h ? h->channels * h->state
 
 int sdsp_iir_get_state(const sdsp_iir* h, void* state, size_t* phase) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuardI g(h->device);
-    IIR_TRY(h->fence.wait(), "wait for queued work");
-    IIR_TRY(hipStreamSynchronize(h->stream), "sync");
+    DeviceGuard g(h->device);
+    if (int st = h->quiesce()) return st;
     const size_t sb = sample_bytes(h->dtype) * h->channels * h->state_per_ch();
-    if (state && sb) IIR_TRY(hipMemcpy(state, h->d_state[h->cur].p, sb, hipMemcpyDeviceToHost), "get state");
+    if (state && sb) SDSP_TRY(hipMemcpy(state, h->state.front(), sb, hipMemcpyDeviceToHost), "get state");
     if (phase) *phase = h->phase;
     return SDSP_OK;
 }
 
 int sdsp_iir_set_state(sdsp_iir* h, const void* state, size_t phase) {
     if (!h || phase >= h->M) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuardI g(h->device);
-    IIR_TRY(h->fence.wait(), "wait for queued work");
-    IIR_TRY(hipStreamSynchronize(h->stream), "sync");
+    DeviceGuard g(h->device);
+    if (int st = h->quiesce()) return st;
     const size_t sb = sample_bytes(h->dtype) * h->channels * h->state_per_ch();
-    if (state && sb) IIR_TRY(hipMemcpy(h->d_state[h->cur].p, state, sb, hipMemcpyHostToDevice), "set state");
+    if (state && sb) SDSP_TRY(hipMemcpy(h->state.front(), state, sb, hipMemcpyHostToDevice), "set state");
     h->phase = phase;
     return SDSP_OK;
 }
@@ -957,10 +891,8 @@ int sdsp_sos_section_coefs(const sdsp_iir* h, int section, double* num2, double*
 
 int sdsp_iir_synchronize(sdsp_iir* h) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuardI g(h->device);
-    IIR_TRY(h->fence.wait(), "wait for queued work");
-    IIR_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    DeviceGuard g(h->device);
+    return h->quiesce();
 }
 
 }  // extern "C"

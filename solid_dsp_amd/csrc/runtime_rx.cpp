@@ -18,41 +18,6 @@ using namespace sdsp;
 
 namespace {
 
-#define R_TRY(expr, what)                                      \
-    do {                                                       \
-        hipError_t _e = (expr);                                \
-        if (_e != hipSuccess) return device_status(_e, what);  \
-    } while (0)
-
-struct Guard {
-    int prev = -1;
-    explicit Guard(int d) {
-        (void)hipGetDevice(&prev);
-        if (prev != d) (void)hipSetDevice(d);
-    }
-    ~Guard() {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-int check_gfx950(int device, int* cus) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) {
-        set_error("no HIP device visible (libsdsp has no CPU execution path)");
-        return SDSP_E_NO_DEVICE;
-    }
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, device) != hipSuccess || std::strncmp(p.gcnArchName, "gfx950", 6) != 0) {
-        set_error("libsdsp is built for gfx950");
-        return SDSP_E_NO_DEVICE;
-    }
-    if (cus) *cus = p.multiProcessorCount;
-    return SDSP_OK;
-}
-
-hipStream_t pick(void* user, hipStream_t own) { return user ? (hipStream_t)user : own; }
 size_t cbytes(int prec) { return prec == 0 ? 8 : 16; }
 int hist_dtype(int prec) { return prec == 0 ? SDSP_RC32 : SDSP_RC64; }  // sample size 8 / 16 bytes
 
@@ -69,32 +34,22 @@ uint32_t constrain(double theta) {
 // ===========================================================================
 // AutoCorrelator
 // ===========================================================================
-struct sdsp_acorr {
-    int prec = 1, device = 0;
+struct sdsp_acorr : HandleCore {
+    int prec = 1;
     size_t W = 0, d = 0, channels = 1;
-    DevBuf hist[2];  // [channels][W] oldest first
-    int cur = 0;
+    PingPong hist;   // [channels][W] oldest first
     DevBuf energy;   // [channels] f64
-    DevBuf stage_in, stage_out;
-    hipStream_t stream = nullptr;
     int kernel = 0;  // SDSP_TUNE_ACORR_KERNEL
-    StreamFence fence;  // the last block queued (on a caller stream or the handle's)
     int K() const { return W > d ? (int)(W - d) : 0; }
 };
 
 namespace {
 int acorr_alloc(sdsp_acorr* h) {
-    const size_t hb = h->channels * h->W * cbytes(h->prec);
-    R_TRY(h->fence.wait(), "wait for queued work");  // a queued block may still read the history
-    for (int i = 0; i < 2; ++i) {
-        R_TRY(h->hist[i].ensure(hb), "alloc history");
-        R_TRY(hipMemsetAsync(h->hist[i].p, 0, hb, h->stream), "zero history");
-    }
-    R_TRY(h->energy.ensure(h->channels * 8), "alloc energy");
-    R_TRY(hipMemsetAsync(h->energy.p, 0, h->channels * 8, h->stream), "zero energy");
-    h->cur = 0;
-    R_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    SDSP_TRY(h->fence.wait(), "wait for queued work");  // a queued block may still read the history
+    SDSP_TRY(h->hist.reset(h->channels * h->W * cbytes(h->prec), h->stream), "zero history");
+    SDSP_TRY(h->energy.ensure(h->channels * 8), "alloc energy");
+    SDSP_TRY(hipMemsetAsync(h->energy.p, 0, h->channels * 8, h->stream), "zero energy");
+    return h->quiesce();
 }
 }  // namespace
 
@@ -111,15 +66,14 @@ int sdsp_acorr_create(sdsp_acorr** out, size_t window_size, size_t delay, int pr
         set_error("window_size / delay too large");
         return SDSP_E_INVALID_ARGUMENT;
     }
-    int st = check_gfx950(device, nullptr);
+    int st = check_device(device, nullptr);
     if (st) return st;
-    Guard g(device);
+    DeviceGuard g(device);
     auto* h = new sdsp_acorr();
     h->prec = precision;
-    h->device = device;
     h->W = window_size;
     h->d = delay;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (h->open(device) != hipSuccess) {
         delete h;
         set_error("hipStreamCreate failed");
         return SDSP_E_DEVICE;
@@ -133,23 +87,7 @@ int sdsp_acorr_create(sdsp_acorr** out, size_t window_size, size_t delay, int pr
     return SDSP_OK;
 }
 
-void sdsp_acorr_destroy(sdsp_acorr* h) {
-    if (!h) return;
-    {
-        Guard g(h->device);
-        (void)h->fence.wait();
-        if (h->stream) {
-            (void)hipStreamSynchronize(h->stream);
-            (void)hipStreamDestroy(h->stream);
-        }
-        h->hist[0].release();
-        h->hist[1].release();
-        h->energy.release();
-        h->stage_in.release();
-        h->stage_out.release();
-    }
-    delete h;
-}
+void sdsp_acorr_destroy(sdsp_acorr* h) { destroy_handle(h); }
 
 int sdsp_acorr_set_tuning(sdsp_acorr* h, int key, int value) {
     if (!h || key != SDSP_TUNE_ACORR_KERNEL || value < 0 || value > 2) return SDSP_E_INVALID_ARGUMENT;
@@ -159,14 +97,14 @@ int sdsp_acorr_set_tuning(sdsp_acorr* h, int key, int value) {
 
 int sdsp_acorr_set_channels(sdsp_acorr* h, size_t channels) {
     if (!h || channels == 0) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     h->channels = channels;
     return acorr_alloc(h);
 }
 
 int sdsp_acorr_reset(sdsp_acorr* h) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     return acorr_alloc(h);
 }
 
@@ -177,46 +115,40 @@ size_t sdsp_acorr_delay(const sdsp_acorr* h) { return h ? h->d : 0; }
 static int acorr_run(sdsp_acorr* h, const void* d_in, size_t n, void* d_out, hipStream_t s) {
     if (n == 0) return SDSP_OK;
     // blocks queued on another stream read and write the history this launch uses
-    R_TRY(h->fence.order_before(s), "order after queued work");
-    const void* hist = h->hist[h->cur].p;
+    SDSP_TRY(h->fence.order_before(s), "order after queued work");
+    const void* hist = h->hist.front();
     if (d_out)
-        R_TRY(launch_acorr(h->prec, d_in, hist, d_out, n, (int)h->W, (int)h->d, h->K(), h->channels, s, h->kernel),
+        SDSP_TRY(launch_acorr(h->prec, d_in, hist, d_out, n, (int)h->W, (int)h->d, h->K(), h->channels, s, h->kernel),
               "acorr");
-    R_TRY(launch_acorr_energy(h->prec, d_in, hist, n, (int)h->W, (int)h->W, h->channels, (double*)h->energy.p, s),
+    SDSP_TRY(launch_acorr_energy(h->prec, d_in, hist, n, (int)h->W, (int)h->W, h->channels, (double*)h->energy.p, s),
           "acorr energy");
-    R_TRY(launch_hist_update(hist_dtype(h->prec), d_in, hist, h->hist[h->cur ^ 1].p, n, (int)h->W, h->channels, s),
+    SDSP_TRY(launch_hist_update(hist_dtype(h->prec), d_in, hist, h->hist.back(), n, (int)h->W, h->channels, s),
           "history update");
-    h->cur ^= 1;
-    R_TRY(h->fence.record(s), "record fence");
+    h->hist.flip();
+    SDSP_TRY(h->fence.record(s), "record fence");
     return SDSP_OK;
 }
 
 int sdsp_acorr_execute_block_device(sdsp_acorr* h, const void* d_in, size_t n, void* d_out, void* stream) {
     if (!h || (n && (!d_in || !d_out))) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     return acorr_run(h, d_in, n, d_out, pick(stream, h->stream));
 }
 
 int sdsp_acorr_write_device(sdsp_acorr* h, const void* d_in, size_t n, void* stream) {
     if (!h || (n && !d_in)) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     return acorr_run(h, d_in, n, nullptr, pick(stream, h->stream));
 }
 
 static int acorr_host(sdsp_acorr* h, const void* in, size_t n, void* out) {
     if (!h || (n && !in)) return SDSP_E_INVALID_ARGUMENT;
     if (n == 0) return SDSP_OK;
-    Guard g(h->device);
-    R_TRY(h->fence.wait(), "wait for queued work");  // host slices: the last block first, on the host
+    DeviceGuard g(h->device);
     const size_t bytes = h->channels * n * cbytes(h->prec);
-    R_TRY(h->stage_in.ensure(bytes), "stage in");
-    R_TRY(hipMemcpyAsync(h->stage_in.p, in, bytes, hipMemcpyHostToDevice, h->stream), "H2D");
-    if (out) R_TRY(h->stage_out.ensure(bytes), "stage out");
-    int st = acorr_run(h, h->stage_in.p, n, out ? h->stage_out.p : nullptr, h->stream);
-    if (st) return st;
-    if (out) R_TRY(hipMemcpyAsync(out, h->stage_out.p, bytes, hipMemcpyDeviceToHost, h->stream), "D2H");
-    R_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    return h->staged(in, bytes, out, out ? bytes : 0, [&](const void* d_in, void* d_out, hipStream_t s) {
+        return acorr_run(h, d_in, n, out ? d_out : nullptr, s);  // a write: no execute() values
+    });
 }
 
 int sdsp_acorr_execute_block(sdsp_acorr* h, const void* in, size_t n, void* out) {
@@ -233,33 +165,31 @@ int sdsp_acorr_push(sdsp_acorr* h, const void* sample) {
 
 int sdsp_acorr_execute(sdsp_acorr* h, void* out) {
     if (!h || !out) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     const size_t bytes = h->channels * cbytes(h->prec);
-    R_TRY(h->stage_out.ensure(bytes), "stage out");
-    R_TRY(h->fence.wait(), "wait for queued work");  // host-side op: wait for the last block on the host
-    R_TRY(launch_acorr_current(h->prec, h->hist[h->cur].p, h->stage_out.p, (int)h->W, (int)h->d, h->K(), h->channels,
+    SDSP_TRY(h->stage_out.ensure(bytes), "stage out");
+    SDSP_TRY(h->fence.wait(), "wait for queued work");  // host-side op: wait for the last block on the host
+    SDSP_TRY(launch_acorr_current(h->prec, h->hist.front(), h->stage_out.p, (int)h->W, (int)h->d, h->K(), h->channels,
                                h->stream),
           "acorr execute");
-    R_TRY(hipMemcpyAsync(out, h->stage_out.p, bytes, hipMemcpyDeviceToHost, h->stream), "D2H");
-    R_TRY(hipStreamSynchronize(h->stream), "sync");
+    SDSP_TRY(hipMemcpyAsync(out, h->stage_out.p, bytes, hipMemcpyDeviceToHost, h->stream), "D2H");
+    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
     return SDSP_OK;
 }
 
 int sdsp_acorr_get_energy(sdsp_acorr* h, double* energy) {
     if (!h || !energy) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
-    R_TRY(h->fence.wait(), "wait for queued work");  // host-side op: wait for the last block on the host
-    R_TRY(hipMemcpyAsync(energy, h->energy.p, h->channels * 8, hipMemcpyDeviceToHost, h->stream), "D2H");
-    R_TRY(hipStreamSynchronize(h->stream), "sync");
+    DeviceGuard g(h->device);
+    SDSP_TRY(h->fence.wait(), "wait for queued work");  // host-side op: wait for the last block on the host
+    SDSP_TRY(hipMemcpyAsync(energy, h->energy.p, h->channels * 8, hipMemcpyDeviceToHost, h->stream), "D2H");
+    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
     return SDSP_OK;
 }
 
 int sdsp_acorr_synchronize(sdsp_acorr* h) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
-    R_TRY(h->fence.wait(), "wait for queued work");
-    R_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    DeviceGuard g(h->device);
+    return h->quiesce();
 }
 
 }  // extern "C"
@@ -267,13 +197,13 @@ int sdsp_acorr_synchronize(sdsp_acorr* h) {
 // ===========================================================================
 // NCO
 // ===========================================================================
-struct sdsp_nco {
-    int device = 0, cus = 256;
+// (records no fence: calls share only the read-only table)
+struct sdsp_nco : HandleCore {
+    int cus = 256;
     uint32_t theta = 0, delta_theta = 0;
     double alpha = 0.1, beta = 0.0;
     double table[1024];
-    DevBuf d_table, stage_in, stage_out;
-    hipStream_t stream = nullptr;
+    DevBuf d_table;
     size_t index() const { return (size_t)(((uint32_t)(theta + (1u << 21)) >> 22) & 0x3ffu); }  // :99-101
 };
 
@@ -283,16 +213,15 @@ int sdsp_nco_create(sdsp_nco** out, int device) {  // NCO::new  src/nco/mod.rs:3
     if (!out) return SDSP_E_INVALID_ARGUMENT;
     *out = nullptr;
     int cus = 256;
-    int st = check_gfx950(device, &cus);
+    int st = check_device(device, &cus);
     if (st) return st;
-    Guard g(device);
+    DeviceGuard g(device);
     auto* h = new sdsp_nco();
-    h->device = device;
     h->cus = cus;
     for (int i = 0; i < 1024; ++i) h->table[i] = std::sin(2.0 * M_PI * (double)i / 1024.0);
     h->alpha = 0.1;
     h->beta = std::sqrt(h->alpha);
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (h->open(device) != hipSuccess) {
         delete h;
         set_error("hipStreamCreate failed");
         return SDSP_E_DEVICE;
@@ -307,20 +236,7 @@ int sdsp_nco_create(sdsp_nco** out, int device) {  // NCO::new  src/nco/mod.rs:3
     return SDSP_OK;
 }
 
-void sdsp_nco_destroy(sdsp_nco* h) {
-    if (!h) return;
-    {
-        Guard g(h->device);
-        if (h->stream) {
-            (void)hipStreamSynchronize(h->stream);
-            (void)hipStreamDestroy(h->stream);
-        }
-        h->d_table.release();
-        h->stage_in.release();
-        h->stage_out.release();
-    }
-    delete h;
-}
+void sdsp_nco_destroy(sdsp_nco* h) { destroy_handle(h); }
 
 int sdsp_nco_reset(sdsp_nco* h) {  // :53-56
     if (!h) return SDSP_E_INVALID_ARGUMENT;
@@ -403,8 +319,8 @@ int sdsp_nco_set_state(sdsp_nco* h, uint32_t theta, uint32_t delta_theta) {
 int sdsp_nco_mix_block_device(sdsp_nco* h, int down, int precision, const void* d_in, size_t n, void* d_out,
                               void* stream) {
     if (!h || (precision != 0 && precision != 1) || (n && (!d_in || !d_out))) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
-    R_TRY(launch_nco_mix(precision, down != 0, d_in, d_out, n, (const double*)h->d_table.p, h->theta, h->delta_theta,
+    DeviceGuard g(h->device);
+    SDSP_TRY(launch_nco_mix(precision, down != 0, d_in, d_out, n, (const double*)h->d_table.p, h->theta, h->delta_theta,
                          h->cus, pick(stream, h->stream)),
           "nco mix");
     h->theta += (uint32_t)((uint64_t)n * h->delta_theta);  // n steps, wrapping
@@ -414,23 +330,17 @@ int sdsp_nco_mix_block_device(sdsp_nco* h, int down, int precision, const void* 
 int sdsp_nco_mix_block(sdsp_nco* h, int down, int precision, const void* in, size_t n, void* out) {
     if (!h || (precision != 0 && precision != 1) || (n && (!in || !out))) return SDSP_E_INVALID_ARGUMENT;
     if (n == 0) return SDSP_OK;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     const size_t bytes = n * cbytes(precision);
-    R_TRY(h->stage_in.ensure(bytes), "stage in");
-    R_TRY(h->stage_out.ensure(bytes), "stage out");
-    R_TRY(hipMemcpyAsync(h->stage_in.p, in, bytes, hipMemcpyHostToDevice, h->stream), "H2D");
-    int st = sdsp_nco_mix_block_device(h, down, precision, h->stage_in.p, n, h->stage_out.p, h->stream);
-    if (st) return st;
-    R_TRY(hipMemcpyAsync(out, h->stage_out.p, bytes, hipMemcpyDeviceToHost, h->stream), "D2H");
-    R_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    return h->staged(in, bytes, out, bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
+        return sdsp_nco_mix_block_device(h, down, precision, d_in, n, d_out, s);
+    });
 }
 
 int sdsp_nco_synchronize(sdsp_nco* h) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
-    R_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    DeviceGuard g(h->device);
+    return h->quiesce();
 }
 
 }  // extern "C"
@@ -438,13 +348,11 @@ int sdsp_nco_synchronize(sdsp_nco* h) {
 // ===========================================================================
 // AGC bank (src/auto_gain_control/mod.rs:97-677)
 // ===========================================================================
-struct sdsp_agc {
-    int device = 0;
+struct sdsp_agc : HandleCore {
     size_t channels = 1;
     std::vector<sdsp_agc_state> host;  // valid when host_valid; the device copy is authoritative after a run
     bool host_valid = true;
-    DevBuf d_state, d_levels, stage_in, stage_out;
-    hipStream_t stream = nullptr, last = nullptr;
+    DevBuf d_state, d_levels;
     bool pipe = true;  // SDSP_TUNE_AGC_KERNEL 0
 };
 
@@ -465,22 +373,22 @@ sdsp_agc_state agc_new_state() {  // AGC::new  :136-149
 }
 int agc_pull(sdsp_agc* h) {
     if (h->host_valid) return SDSP_OK;
-    if (h->last) R_TRY(hipStreamSynchronize(h->last), "sync");
-    R_TRY(hipMemcpy(h->host.data(), h->d_state.p, h->channels * sizeof(sdsp_agc_state), hipMemcpyDeviceToHost),
+    if (int st = h->quiesce()) return st;
+    SDSP_TRY(hipMemcpy(h->host.data(), h->d_state.p, h->channels * sizeof(sdsp_agc_state), hipMemcpyDeviceToHost),
           "state D2H");
     h->host_valid = true;
     return SDSP_OK;
 }
 int agc_push(sdsp_agc* h) {
-    if (h->last) R_TRY(hipStreamSynchronize(h->last), "sync");
-    R_TRY(hipMemcpy(h->d_state.p, h->host.data(), h->channels * sizeof(sdsp_agc_state), hipMemcpyHostToDevice),
+    if (int st = h->quiesce()) return st;
+    SDSP_TRY(hipMemcpy(h->d_state.p, h->host.data(), h->channels * sizeof(sdsp_agc_state), hipMemcpyHostToDevice),
           "state H2D");
     return SDSP_OK;
 }
 // read-modify-write every channel's state
 template <typename F> int agc_update(sdsp_agc* h, F f) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     int st = agc_pull(h);
     if (st) return st;
     for (auto& s : h->host) f(s);
@@ -498,14 +406,13 @@ int sdsp_agc_create(sdsp_agc** out, size_t channels, int device) {
         set_error("channels must be > 0");
         return SDSP_E_INVALID_ARGUMENT;
     }
-    int st = check_gfx950(device, nullptr);
+    int st = check_device(device, nullptr);
     if (st) return st;
-    Guard g(device);
+    DeviceGuard g(device);
     auto* h = new sdsp_agc();
-    h->device = device;
     h->channels = channels;
     h->host.assign(channels, agc_new_state());
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (h->open(device) != hipSuccess) {
         delete h;
         set_error("hipStreamCreate failed");
         return SDSP_E_DEVICE;
@@ -519,22 +426,7 @@ int sdsp_agc_create(sdsp_agc** out, size_t channels, int device) {
     return SDSP_OK;
 }
 
-void sdsp_agc_destroy(sdsp_agc* h) {
-    if (!h) return;
-    {
-        Guard g(h->device);
-        if (h->last) (void)hipStreamSynchronize(h->last);
-        if (h->stream) {
-            (void)hipStreamSynchronize(h->stream);
-            (void)hipStreamDestroy(h->stream);
-        }
-        h->d_state.release();
-        h->d_levels.release();
-        h->stage_in.release();
-        h->stage_out.release();
-    }
-    delete h;
-}
+void sdsp_agc_destroy(sdsp_agc* h) { destroy_handle(h); }
 
 size_t sdsp_agc_channels(const sdsp_agc* h) { return h ? h->channels : 0; }
 
@@ -557,11 +449,12 @@ int sdsp_agc_execute_block_device(sdsp_agc* h, int sample_type, const void* d_in
                                   void* stream) {
     if (!h || (sample_type != 0 && sample_type != 1) || (n && (!d_in || !d_out))) return SDSP_E_INVALID_ARGUMENT;
     if (n == 0) return SDSP_OK;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     hipStream_t s = pick(stream, h->stream);
-    if (h->last && h->last != s) R_TRY(hipStreamSynchronize(h->last), "sync");  // state hand-off between streams
-    R_TRY(launch_agc(sample_type == 1, d_in, d_out, n, h->d_state.p, h->channels, s, h->pipe), "agc");
-    h->last = s;
+    // a block queued on another stream (the fence) reads and writes the state this launch uses
+    SDSP_TRY(h->fence.order_before(s), "order after queued work");
+    SDSP_TRY(launch_agc(sample_type == 1, d_in, d_out, n, h->d_state.p, h->channels, s, h->pipe), "agc");
+    SDSP_TRY(h->fence.record(s), "record fence");
     h->host_valid = false;
     return SDSP_OK;
 }
@@ -569,16 +462,11 @@ int sdsp_agc_execute_block_device(sdsp_agc* h, int sample_type, const void* d_in
 int sdsp_agc_execute_block(sdsp_agc* h, int sample_type, const void* in, size_t n, void* out) {
     if (!h || (sample_type != 0 && sample_type != 1) || (n && (!in || !out))) return SDSP_E_INVALID_ARGUMENT;
     if (n == 0) return SDSP_OK;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     const size_t bytes = h->channels * n * agc_bytes(sample_type);
-    R_TRY(h->stage_in.ensure(bytes), "stage in");
-    R_TRY(h->stage_out.ensure(bytes), "stage out");
-    R_TRY(hipMemcpyAsync(h->stage_in.p, in, bytes, hipMemcpyHostToDevice, h->stream), "H2D");
-    int st = sdsp_agc_execute_block_device(h, sample_type, h->stage_in.p, n, h->stage_out.p, h->stream);
-    if (st) return st;
-    R_TRY(hipMemcpyAsync(out, h->stage_out.p, bytes, hipMemcpyDeviceToHost, h->stream), "D2H");
-    R_TRY(hipStreamSynchronize(h->stream), "sync");
-    return SDSP_OK;
+    return h->staged(in, bytes, out, bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
+        return sdsp_agc_execute_block_device(h, sample_type, d_in, n, d_out, s);
+    });
 }
 
 int sdsp_agc_init(sdsp_agc* h, int sample_type, const void* in, size_t n, double* levels) {
@@ -587,21 +475,21 @@ int sdsp_agc_init(sdsp_agc* h, int sample_type, const void* in, size_t n, double
         set_error("AGC Error Need more than 0 Samples to operate");
         return SDSP_E_AGC_SAMPLES_TOO_LOW;
     }
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     int st = agc_pull(h);
     if (st) return st;
     const size_t bytes = h->channels * n * agc_bytes(sample_type);
-    R_TRY(h->stage_in.ensure(bytes), "stage in");
-    R_TRY(h->d_levels.ensure(h->channels * 8), "levels");
-    if (h->last && h->last != h->stream) R_TRY(hipStreamSynchronize(h->last), "sync");
-    R_TRY(hipMemcpyAsync(h->stage_in.p, in, bytes, hipMemcpyHostToDevice, h->stream), "H2D");
-    R_TRY(launch_agc_init(sample_type == 1, h->stage_in.p, n, h->d_state.p, (double*)h->d_levels.p, h->channels,
+    SDSP_TRY(h->stage_in.ensure(bytes), "stage in");
+    SDSP_TRY(h->d_levels.ensure(h->channels * 8), "levels");
+    st = h->quiesce();  // the kernel below reads and writes the state of a block queued on any stream
+    if (st) return st;
+    SDSP_TRY(hipMemcpyAsync(h->stage_in.p, in, bytes, hipMemcpyHostToDevice, h->stream), "H2D");
+    SDSP_TRY(launch_agc_init(sample_type == 1, h->stage_in.p, n, h->d_state.p, (double*)h->d_levels.p, h->channels,
                           h->stream),
           "agc init");
     std::vector<double> lv(h->channels);
-    R_TRY(hipMemcpyAsync(lv.data(), h->d_levels.p, h->channels * 8, hipMemcpyDeviceToHost, h->stream), "D2H");
-    R_TRY(hipStreamSynchronize(h->stream), "sync");
-    h->last = h->stream;
+    SDSP_TRY(hipMemcpyAsync(lv.data(), h->d_levels.p, h->channels * 8, hipMemcpyDeviceToHost, h->stream), "D2H");
+    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
     h->host_valid = false;
     if (levels) std::memcpy(levels, lv.data(), h->channels * 8);
     for (double l : lv)
@@ -694,7 +582,7 @@ int sdsp_agc_squelch_set_timeout(sdsp_agc* h, uint64_t timeout) {
 
 int sdsp_agc_get_state(sdsp_agc* h, size_t channel, sdsp_agc_state* st) {
     if (!h || !st || channel >= h->channels) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     int r = agc_pull(h);
     if (r) return r;
     *st = h->host[channel];
@@ -702,7 +590,7 @@ int sdsp_agc_get_state(sdsp_agc* h, size_t channel, sdsp_agc_state* st) {
 }
 int sdsp_agc_set_state(sdsp_agc* h, size_t channel, const sdsp_agc_state* st) {
     if (!h || !st || channel >= h->channels) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
+    DeviceGuard g(h->device);
     int r = agc_pull(h);
     if (r) return r;
     h->host[channel] = *st;
@@ -710,9 +598,8 @@ int sdsp_agc_set_state(sdsp_agc* h, size_t channel, const sdsp_agc_state* st) {
 }
 int sdsp_agc_synchronize(sdsp_agc* h) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    Guard g(h->device);
-    if (h->last) R_TRY(hipStreamSynchronize(h->last), "sync");
-    return SDSP_OK;
+    DeviceGuard g(h->device);
+    return h->quiesce();
 }
 
 }  // extern "C"

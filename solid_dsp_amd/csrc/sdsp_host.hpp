@@ -1,4 +1,4 @@
-// Internal host-side helpers shared by runtime.cpp and design.cpp.
+// Internal host-side helpers shared by the runtime units (runtime*.cpp) and design.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -6,6 +6,8 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include "sdsp.h"
 
 namespace sdsp {
 
@@ -24,6 +26,32 @@ void set_error(const std::string& msg);
 // the algorithm new FIR-type and IIR handles start on (sdsp_set_default_algo; SDSP_DEFAULT_ALGO)
 int default_algo();
 int device_status(hipError_t e, const char* what);
+#define SDSP_TRY(expr, what)                                  \
+    do {                                                      \
+        hipError_t _e = (expr);                               \
+        if (_e != hipSuccess) return device_status(_e, what); \
+    } while (0)
+
+// SDSP_OK when `device` is a usable gfx950 device, SDSP_E_NO_DEVICE otherwise; *cus (when given)
+// receives its compute-unit count
+int check_device(int device, int* cus);
+
+// makes `d` the calling thread's device for a scope and puts the caller's back
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int d) {
+        (void)hipGetDevice(&prev);
+        if (prev != d) (void)hipSetDevice(d);
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+// the stream a call runs on: the caller's, or the handle's own when none is given
+inline hipStream_t pick(void* user, hipStream_t own) { return user ? (hipStream_t)user : own; }
 
 // dtype traits (sdsp_dtype)
 inline size_t sample_bytes(int dt) {
@@ -48,7 +76,6 @@ inline cd coef_at(const unsigned char* p, int dt, size_t i) {
     return {0.0, 0.0};
 }
 
-// owned device allocation
 // pinned host memory mapped into the device address space (coherent): a kernel
 // writes it directly, the host reads it after the stream synchronises
 struct HostMapped {
@@ -84,6 +111,7 @@ inline hipError_t wait_host_flag(const unsigned* flag, unsigned seq, hipStream_t
     return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq ? hipSuccess : hipErrorUnknown;
 }
 
+// owned device allocation
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
@@ -116,10 +144,13 @@ struct DevBuf {
 // (a caller's stream or the handle's own).  *_execute_block_device may run on any
 // stream: each launch is first ordered after the marker (order_before) and then
 // records a new one (record), so a call on a caller stream s1, a call on the handle
-// stream and another call on s1 run in that order.  Host-side state operations
-// (reset, set_state / get_state, clone, table rebuilds after set_scale) first wait
-// for the marker, so a kernel still reading the delay line or the tables is never
-// raced by a host copy on the handle's own stream.
+// stream and another call on s1 run in that order.  Host-side operations (the
+// host-slice entry points, reset and the other state reallocations, set_state /
+// get_state, clone, table rebuilds after set_scale, *_synchronize and destroy) first
+// wait for the marker (HandleCore::quiesce, HandleCore::staged), so a kernel still
+// reading the delay line or the tables is never raced by a host copy on the handle's
+// own stream, or by a free.  The fir, pfb, iir, chan, acorr and agc handles record
+// it; the fft and nco handles do not (the boundary).
 //
 // The markers rotate through kRing events: a stream never re-records the event it
 // has just waited on (a stream waiting on an event that it then re-records every
@@ -174,6 +205,76 @@ struct StreamFence {
         return e;
     }
 };
+
+// Delay-line state that a kernel reads from one buffer and writes to the other: front() is the
+// current state, back() the one the next launch writes, flip() after that launch
+struct PingPong {
+    DevBuf buf[2];
+    int cur = 0;
+    void* front() const { return buf[cur].p; }
+    void* back() const { return buf[cur ^ 1].p; }
+    void flip() { cur ^= 1; }
+    // both halves hold `bytes` zeroed bytes (queued on `s`), front() is the first
+    hipError_t reset(size_t bytes, hipStream_t s) {
+        for (DevBuf& b : buf) {
+            hipError_t e = b.ensure(bytes);
+            if (e == hipSuccess && bytes) e = hipMemsetAsync(b.p, 0, bytes, s);
+            if (e != hipSuccess) return e;
+        }
+        cur = 0;
+        return hipSuccess;
+    }
+};
+
+// What every handle of the C ABI owns besides its own tables and state: its device, a
+// non-blocking stream, the fence of the last block it queued and the staging buffers of its
+// host-slice entry points.  Every handle struct derives from it.
+struct HandleCore {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    mutable StreamFence fence;
+    DevBuf stage_in, stage_out;
+
+    hipError_t open(int dev) {
+        device = dev;
+        return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+    }
+    // nothing the handle queued is running any more, on a caller's stream or its own: the body of
+    // every *_synchronize, and what state reads, writes, reallocations and destroy wait for first
+    int quiesce() const {
+        SDSP_TRY(fence.wait(), "wait for queued work");
+        SDSP_TRY(hipStreamSynchronize(stream), "sync");
+        return SDSP_OK;
+    }
+    // A host-slice entry point: in -> stage_in, run(d_in, d_out, stream) -> status, stage_out -> out
+    // (when out_bytes and run returned 0), synchronised.  The fence wait comes first for every
+    // handle: the call is synchronous and run() orders itself after the fence anyway, so waiting
+    // here changes nothing observable and keeps the staging copies out of a queued block's way.
+    template <typename Run> int staged(const void* in, size_t in_bytes, void* out, size_t out_bytes, Run run) {
+        SDSP_TRY(fence.wait(), "wait for queued work");
+        SDSP_TRY(stage_in.ensure(in_bytes), "stage in");
+        SDSP_TRY(stage_out.ensure(out_bytes), "stage out");
+        SDSP_TRY(hipMemcpyAsync(stage_in.p, in, in_bytes, hipMemcpyHostToDevice, stream), "H2D");
+        const int st = run(stage_in.p, stage_out.p, stream);
+        if (st) return st;
+        if (out_bytes) SDSP_TRY(hipMemcpyAsync(out, stage_out.p, out_bytes, hipMemcpyDeviceToHost, stream), "D2H");
+        SDSP_TRY(hipStreamSynchronize(stream), "sync");
+        return SDSP_OK;
+    }
+};
+
+// The body of every *_destroy.  The order matters: the waits come before any free, because work
+// queued on a caller stream may still read the tables and the history; and the handle is deleted
+// inside the guard's scope, so every DevBuf member frees under the handle's device.
+template <typename H> void destroy_handle(H* h) {
+    if (!h) return;
+    DeviceGuard g(h->device);
+    if (h->stream) {  // (no stream: create failed before anything was queued)
+        (void)h->quiesce();
+        (void)hipStreamDestroy(h->stream);
+    }
+    delete h;
+}
 
 // [a, a + na) and [b, b + nb) overlap (byte ranges)
 inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {

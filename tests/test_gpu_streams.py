@@ -211,6 +211,181 @@ def test_chan_blocks_across_streams_run_in_call_order(order):
             assert rel_rms(y[s], ref) <= 1e-6, (k, s)
 
 
+def _dev_synth(seed, channels, n, dt=C64):
+    """[channels, n] complex stream generated on the device (the synthetic stream of SURVEY §8d)"""
+    import torch
+    x = torch.empty((channels, n), dtype=torch.complex64, device="cuda")
+    for c in range(channels):
+        sd.lib().sdsp_synth_f32_device(x[c].data_ptr(), seed, c, 0, 2 * n, None)
+    torch.cuda.synchronize()
+    return x if dt == C64 else x.to(torch.complex128)
+
+
+def _sync_fir(n):
+    h = O.firdes_kaiser(64, 0.1, 80.0, 0.0).astype(F32)
+    f = sd.FIRFilter(h, F32(0.2), sample_dtype=C64, algo=sd.ALGO_EXACT, host_step=False)
+    x, y = _dev_synth(77, 1, n)[0], empty_dev(n, C64)
+    mk = lambda: O.fir(O.RC32, h, F32(0.2))
+
+    def check():
+        xh, xt = to_host(x[:N2]), to_host(x[n - N2 - 63:])
+        assert bits_equal(to_host(y[:N2]), mk().execute_block(xh))
+        assert bits_equal(to_host(y[n - N2:]), mk().execute_block(xt)[63:])
+    return f, (lambda s: f.execute_block_device(x, n, y, s)), check
+
+
+def _sync_pfb(n):
+    M, K, m = 16, 8, 512
+    h = np.random.default_rng(4).standard_normal(M * K).astype(F32)
+    p = sd.PolyPhaseFilterBank(h, M, 1.0, sample_dtype=C64, coef_dtype=F32)
+    x, y = _dev_synth(79, 1, n)[0], empty_dev(n * M, C64)
+    mk = lambda: O.pfb(O.RC32, h, M, F32(1.0))
+
+    def check():
+        assert bits_equal(to_host(y[:m * M]), mk().execute_block(to_host(x[:m])))
+        assert bits_equal(to_host(y[(n - m) * M:]), mk().execute_block(to_host(x[n - m - K:]))[K * M:])
+    return p, (lambda s: p.execute_block_device(x, n, y, s)), check
+
+
+def _sync_iir(n):
+    import json
+    import os
+    sos = np.array(json.load(open(os.path.join(os.path.dirname(__file__), "golden", "butter8_0p2_sos.json")))["sos"])
+    ff, fb = sos[:, :3].reshape(-1), sos[:, 3:].reshape(-1)
+    f = sd.IIRFilter(ff, fb, sd.IIRFilterType.SecondOrder, sample_dtype=F64, algo=sd.ALGO_EXACT)
+    xh = O.synth(80, 0, 0, n).astype(F64)
+    x, y = to_dev(xh), empty_dev(n, F64)
+
+    def check():
+        assert bits_equal(to_host(y), O.iir(O.RR64, ff, fb, 1).execute_block(xh))
+    return f, (lambda s: f.execute_block_device(x, n, y, s)), check
+
+
+def _sync_chan(frames):
+    from solid_dsp_amd.channelizer import Channelizer
+    M, K, S, m = 1024, 8, 2, 16
+    h = O.firdes_kaiser(M * K, 0.5 / M, 80.0, 0.0).astype(F32)
+    ch = Channelizer(h, M, sample_dtype=C64, streams=S)
+    n = frames * M
+    x, y = _dev_synth(82, S, n), empty_dev(S * n, C64)
+
+    def ref(xs):
+        r = np.zeros(len(xs), C128)
+        O.lib().orc_channelize(O._ptr(h.astype(F64)), len(h), M, O._ptr(xs.astype(C128)), len(xs), O._ptr(r))
+        return r.reshape(-1, M)
+
+    def check():
+        yv = y.view(S, frames, M)
+        for s in range(S):
+            assert rel_rms(to_host(yv[s, :m]), ref(to_host(x[s, :m * M]))) <= 1e-6, s
+            tail = ref(to_host(x[s, n - (m + K - 1) * M:]))[K - 1:]
+            assert rel_rms(to_host(yv[s, frames - m:]), tail) <= 1e-6, s
+    return ch, (lambda s: ch.execute_block_device(x.view(-1), n, y, s)), check
+
+
+def _sync_acorr(n):
+    g = sd.AutoCorrelator(64, 16, dtype=C128)
+    x, y = _dev_synth(81, 1, n, C128)[0], empty_dev(n, C128)
+    mk = lambda: O.AutoCorr(64, 16, C128)
+
+    def check():
+        assert to_host(y[:N2]).tobytes() == mk().execute_block(to_host(x[:N2])).tobytes()
+        # the window and its delayed copy hold the last 64 + 16 inputs: N2 more than refill them
+        assert to_host(y[n - N2:]).tobytes() == mk().execute_block(to_host(x[n - 2 * N2:]))[N2:].tobytes()
+    return g, (lambda s: g.execute_block_device(x, n, y, s)), check
+
+
+def _sync_agc(n):
+    import torch
+    from test_gpu_rx import _close
+    rng = np.random.default_rng(41)
+    xh = ((rng.standard_normal((4, n)) + 1j * rng.standard_normal((4, n))) * 0.05).astype(C128)
+    g = sd.AGC(channels=4)
+    g.set_bandwidth(0.05)
+    x = to_dev(xh)
+    y = torch.empty_like(x)
+
+    def check():
+        yh = to_host(y)
+        for c in range(4):
+            o = O.Agc()
+            o.set_bandwidth(0.05)
+            assert _close(yh[c], o.execute_block(xh[c])), c
+    return g, (lambda s: g.execute_block_device(x, n, y, complex_=True, stream=s)), check
+
+
+@pytest.mark.parametrize("make,n", [(_sync_pfb, 1 << 26), (_sync_fir, 1 << 28), (_sync_iir, 1 << 18),
+                                    (_sync_chan, 1 << 18), (_sync_acorr, 1 << 28), (_sync_agc, 1 << 16)],
+                         ids=["pfb", "fir", "iir", "chan", "acorr", "agc"])
+def test_synchronize_covers_a_block_on_a_caller_stream(make, n):
+    """handle.synchronize() returns only after a block queued on a caller's stream has finished:
+    the block is staged, queued on a fresh stream through the _device call, and after
+    synchronize() the stream has nothing left to run (stream.query()).  Then the block against
+    the restatement as in the chain tests: bit for bit (EXACT / serial kernels), rel-RMS 1e-6
+    (channeliser), AGC_RTOL (AGC); the iir and agc blocks whole, the others over their first and
+    last 4096 samples (512 inputs for the pfb, 16 frames for the channeliser), the last ones from a
+    fresh restatement fed the inputs its window needs -- the restatement cannot walk 2^26 to 2^28
+    samples within a test.
+
+    Block lengths: the pfb, fir, chan and acorr blocks of 2^20, 2^22, 256 frames and 2^20 samples
+    run 0.07, 0.07, 0.05 and 0.03 ms, so they are doubled until they pass 1 ms.  One block on the
+    parent build, a pair of events around the call (MI355X, ms; the handle's first call, then the
+    same block again):
+      pfb   M = 16, K = 8, c32, 2^26 inputs            1.80   1.73
+      fir   EXACT, 64 taps, c32, 2^28 samples          1.57   1.67
+      iir   butter8 SOS, f64, serial, 2^18 samples    91.4   86.7
+      chan  M = 1024, K = 8, 2 streams, 2^18 frames    4.75   1.60
+      acorr (64, 16), c64, 2^28 samples                3.18   2.13
+      agc   4 channels x 2^16 Complex<f64>            28.8   28.8
+    On the parent build the pfb case fails at stream.query() (sdsp_pfb_synchronize did not wait
+    for the fence); the other five pass there.
+    """
+    import torch
+    h, queue, check = make(n)
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    queue(s)
+    h.synchronize()
+    assert s.query()
+    check()
+    del h, queue, check
+    torch.cuda.empty_cache()  # up to 9 GB of blocks: not kept for the rest of the session
+
+
+@pytest.mark.parametrize("order", ORDERS)
+def test_agc_blocks_across_streams_run_in_call_order(order):
+    """4-channel AGC bank, bandwidth 0.05, Complex<f64>: a 2^16-sample block, then three of 512,
+    the input amplitude stepping between blocks so that the gain each block starts from matters;
+    every block per channel against the restatement run over the whole stream, and the state the
+    chain leaves (get_state through the fence) against the restatement's"""
+    from test_gpu_rx import AGC_RTOL, _close
+    rng = np.random.default_rng(42)
+    ch, lens, amps = 4, [1 << 16, 512, 512, 512], [0.05, 0.5, 0.005, 0.2]
+    x = np.concatenate([((rng.standard_normal((ch, m)) + 1j * rng.standard_normal((ch, m))) * a).astype(C128)
+                        for m, a in zip(lens, amps)], axis=1)
+    cuts = np.cumsum([0] + lens)
+    g = sd.AGC(channels=ch)
+    g.set_bandwidth(0.05)
+
+    def run(i, n, o, st):
+        g.execute_block_device(i, n // ch, o, complex_=True, stream=st)
+        return n
+
+    blocks = [np.ascontiguousarray(x[:, a:b]).reshape(-1) for a, b in zip(cuts[:-1], cuts[1:])]
+    outs = _chain(run, blocks, lambda n: n, C128, order)
+    st0 = g.state(0)
+    for c in range(ch):
+        o = O.Agc()
+        o.set_bandwidth(0.05)
+        ref = o.execute_block(x[c])
+        for k in range(4):
+            assert _close(outs[k].reshape(ch, -1)[c], ref[cuts[k]:cuts[k + 1]]), (c, k)
+        if c == 0:
+            assert abs(st0.gain - o.get_gain()) <= AGC_RTOL * o.get_gain()
+            assert abs(st0.energy_estimate - o.get_energy()) <= AGC_RTOL * o.get_energy()
+            assert st0.squelch_mode == o.get_mode() and st0.squelch_timer == o.get_timer()
+
+
 @pytest.mark.parametrize("kernel", [0, 1])
 def test_agc_kernel_variants_agree(kernel):
     import torch
