@@ -61,12 +61,16 @@ typedef enum {
  * by default every result is bit-identical to the reference algorithm at the handle's
  * precision, whatever the block size.  The fast kernels are opt-in. */
 typedef enum {
-    SDSP_ALGO_AUTO = 0,  /* FFT overlap-save for 32-bit complex blocks >= 65536 samples, else EXACT */
+    SDSP_ALGO_AUTO = 0,  /* FFT overlap-save for 32-bit complex blocks >= 65536 samples (taps up to
+                            2^20 + 1, no decimation), else EXACT */
     SDSP_ALGO_EXACT = 1, /* direct form in the reference summation order, no FMA contraction:
                             bit-identical to the reference algorithm at the handle's precision */
     SDSP_ALGO_FMA = 2,   /* direct form, same order, fused multiply-add                      */
-    SDSP_ALGO_FFT = 3    /* overlap-save fast convolution (N = 4096) in LDS: 32-bit complex samples,
-                            and real f32 samples with real f32 taps (two real segments per transform) */
+    SDSP_ALGO_FFT = 3    /* overlap-save fast convolution, no decimation.  Up to 3841 taps: N = 4096 in
+                            LDS, 32-bit complex samples, and real f32 samples with real f32 taps (two
+                            real segments per transform).  3842 to 2^20 + 1 taps, 32-bit complex
+                            samples: one N-point transform per segment in three passes, N the power
+                            of two >= 4 (len - 1) and >= 2^14 (sdsp_fir_ols_info) */
 } sdsp_algo;
 
 typedef enum {
@@ -128,6 +132,9 @@ SDSP_API int sdsp_decim_create(sdsp_fir** out, int dtype, const void* taps, size
                                const void* scale, size_t decimation, int device);
 /* channel count (default 1); resets the delay lines */
 SDSP_API int sdsp_fir_set_channels(sdsp_fir* h, size_t channels);
+/* SDSP_ALGO_FFT on a handle it does not cover (64-bit dtypes, decimators, real f32 samples with
+ * more than 3841 taps, more than 2^20 + 1 taps) fails with SDSP_E_UNSUPPORTED; every block of a
+ * handle set to it takes the overlap-save path, whatever its length */
 SDSP_API int sdsp_fir_set_algo(sdsp_fir* h, int algo);
 SDSP_API int sdsp_fir_get_algo(const sdsp_fir* h); /* resolved algorithm */
 /* Process-wide starting algorithm of handles created afterwards (sdsp_fir_create,
@@ -181,8 +188,13 @@ typedef enum {
                                       and window <= 128), one-shot kernel elsewhere; 1 the one-shot kernel
                                       everywhere, delayed input staged in LDS (delay <= 256); 2 the one-shot
                                       kernel with two loads per product */
-    SDSP_TUNE_AGC_KERNEL = 21      /* AGC bank: 0 (default) pipelined kernel for calls < 2^22 samples per
+    SDSP_TUNE_AGC_KERNEL = 21,     /* AGC bank: 0 (default) pipelined kernel for calls < 2^22 samples per
                                       channel, 1 the plain per-sample kernel */
+    SDSP_TUNE_OLS_LONG_LOG2N = 22, /* overlap-save with more than 3841 taps: log2 of the segment transform
+                                      size N, 13..22 with N >= 2 (len - 1); 0 (default) = the smallest
+                                      power of two >= 4 (len - 1) and >= 2^14.  Other handles accept 0 only */
+    SDSP_TUNE_OLS_LONG_SEGS = 23   /* the same path: segments per round of its three passes, 1..4096;
+                                      0 (default) = what 256 MiB of scratch hold */
 } sdsp_tune_key;
 SDSP_API int sdsp_fir_set_tuning(sdsp_fir* h, int key, int value);
 SDSP_API void sdsp_fir_destroy(sdsp_fir* h);        /* Drop */
@@ -191,6 +203,10 @@ SDSP_API int sdsp_fir_clone(const sdsp_fir* h, sdsp_fir** out);
 /* set_scale / get_scale                              fir/mod.rs:103-124, decim.rs:57-78 */
 SDSP_API int sdsp_fir_set_scale(sdsp_fir* h, const void* scale);
 SDSP_API int sdsp_fir_get_scale(const sdsp_fir* h, void* scale);
+/* segment transform size and outputs per segment that SDSP_ALGO_FFT would use on this handle
+ * (no reference counterpart): 4096 and 4096 - 256 ceil((len - 1) / 256) up to 3841 taps, N and
+ * N - (len - 1) above (SDSP_TUNE_OLS_LONG_LOG2N), both 0 where overlap-save does not apply */
+SDSP_API int sdsp_fir_ols_info(const sdsp_fir* h, size_t* nfft, size_t* valid);
 /* len (fir/mod.rs:139-142), get_decimation (decim.rs:92-95) */
 SDSP_API size_t sdsp_fir_len(const sdsp_fir* h);
 SDSP_API size_t sdsp_fir_decimation(const sdsp_fir* h);

@@ -42,6 +42,8 @@ pub const SDSP_ALGO_FFT: c_int = 3;
 
 pub const SDSP_TUNE_HOST_STEP: c_int = 16;
 pub const SDSP_TUNE_HOST_BLOCK_MACS: c_int = 17;
+pub const SDSP_TUNE_OLS_LONG_LOG2N: c_int = 22;
+pub const SDSP_TUNE_OLS_LONG_SEGS: c_int = 23;
 
 pub const SDSP_OK: c_int = 0;
 pub const SDSP_E_COEFFICIENTS_LENGTH_ZERO: c_int = 1;
@@ -82,6 +84,7 @@ extern "C" {
     pub fn sdsp_fir_synchronize(h: *mut sdsp_fir) -> c_int;
     pub fn sdsp_fir_set_scale(h: *mut sdsp_fir, scale: *const c_void) -> c_int;
     pub fn sdsp_fir_get_scale(h: *const sdsp_fir, scale: *mut c_void) -> c_int;
+    pub fn sdsp_fir_ols_info(h: *const sdsp_fir, nfft: *mut usize, valid: *mut usize) -> c_int;
     pub fn sdsp_fir_len(h: *const sdsp_fir) -> usize;
     pub fn sdsp_fir_decimation(h: *const sdsp_fir) -> usize;
     pub fn sdsp_fir_coefficients(h: *const sdsp_fir, out: *mut c_void) -> c_int;

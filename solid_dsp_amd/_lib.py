@@ -24,6 +24,7 @@ TUNE_IIR_WAVE_SCAN, TUNE_CHAN_STREAMING, TUNE_CHAN_FRAMES_PER_BLOCK = 7, 8, 9
 TUNE_OLS_KERNEL, TUNE_CHAN_XCD_ORDER = 14, 15
 TUNE_HOST_STEP, TUNE_HOST_BLOCK_MACS = 16, 17
 TUNE_FFT_GROUP, TUNE_FFT_WAVE1024, TUNE_ACORR_KERNEL, TUNE_AGC_KERNEL = 18, 19, 20, 21
+TUNE_OLS_LONG_LOG2N, TUNE_OLS_LONG_SEGS = 22, 23
 
 _PAIRS = {
     (np.dtype(np.float32), np.dtype(np.float32)): RR32,
@@ -92,6 +93,7 @@ def _declare(L):
         "sdsp_fir_clone": (i, [vp, vpp]),
         "sdsp_fir_set_scale": (i, [vp, vp]),
         "sdsp_fir_get_scale": (i, [vp, vp]),
+        "sdsp_fir_ols_info": (i, [vp, szp, szp]),
         "sdsp_fir_len": (sz, [vp]),
         "sdsp_fir_decimation": (sz, [vp]),
         "sdsp_fir_coefficients": (i, [vp, vp]),

@@ -107,6 +107,11 @@ struct sdsp_fir : HandleCore {
     int decim_seg = 0;  // outputs per lane group of the polyphase decimator (0 = auto)
     OlsPlan ols{};
     DevBuf d_H, d_tw1, d_tw2, d_pkt, d_ostab, d_hhalf;
+    // long filters (L - 1 > 3840, c32 samples): the three-pass plan of kern_fir_ols_long.hip
+    int long_log2n = 0;  // SDSP_TUNE_OLS_LONG_LOG2N (0 = automatic)
+    int long_segs = 0;   // SDSP_TUNE_OLS_LONG_SEGS (0 = automatic)
+    OlsLongPlan olsl{};
+    DevBuf d_lG, d_ltw, d_ltmp;  // spectrum [N1][N2], tables [N1 | N2], scratch [segments][N]
 };
 
 namespace {
@@ -127,13 +132,85 @@ int fir_alloc_state(sdsp_fir* h) {
 // real f32 samples with real f32 taps run the packed-pair kernel (kern_fir_ols_real.hip)
 bool ols_real(const sdsp_fir* h) { return h->dtype == SDSP_RR32; }
 
-bool ols_applicable(const sdsp_fir* h) {
+// the 4096-point one-workgroup segment kernels
+bool ols_short(const sdsp_fir* h) {
     return (h->dtype == SDSP_RR32 || h->dtype == SDSP_RC32 || h->dtype == SDSP_CC32) && h->M == 1 && h->L >= 2 &&
            h->L - 1 <= 256 * 15;
+}
+// longer taps on c32 samples: the three-pass segment transform (kern_fir_ols_long.hip)
+bool ols_long(const sdsp_fir* h) {
+    return (h->dtype == SDSP_RC32 || h->dtype == SDSP_CC32) && h->M == 1 && h->L - 1 > 256 * 15 &&
+           h->L - 1 <= kOlsLongMaxLm1;
+}
+bool ols_applicable(const sdsp_fir* h) { return ols_short(h) || ols_long(h); }
+
+// AUTO moves a long-filter c32 block to the three-pass path from this many samples
+// (profiles/r10/LAB.md: the A/B against the reference-order kernel at L = 3842)
+constexpr size_t kOlsLongAutoMin = (size_t)1 << 16;
+
+// log2 of the long path's transform size: the tuned value, else the smallest power of two
+// >= 4 (L-1) and >= 2^14 (at least three quarters of every transform is output)
+int ols_long_log2n(const sdsp_fir* h) {
+    if (h->long_log2n) return h->long_log2n;
+    int lg = 14;
+    while (((size_t)1 << lg) < 4 * (h->L - 1)) ++lg;
+    return lg;
+}
+
+// spectrum of g[i] = scale * h[L-1-i], zero-padded to N, over N, in [k1][k2] order
+// (k = k1 + N1 k2), and the tables of the N1- and N2-point transforms
+int ols_long_build(sdsp_fir* h) {
+    SDSP_TRY(h->fence.wait(), "wait for queued work");
+    const int lg = ols_long_log2n(h), l1 = lg / 2, l2 = lg - l1;
+    const size_t N = (size_t)1 << lg, N1 = (size_t)1 << l1, N2 = (size_t)1 << l2, L = h->L;
+    std::vector<double> g(2 * N, 0.0);
+    const cd s = coef_at(h->scale.data(), h->dtype, 0);
+    for (size_t i = 0; i < L; ++i) {
+        const cd c = coef_at(h->taps.data(), h->dtype, L - 1 - i);
+        const cd v = coef_is_complex(h->dtype) ? cmul(c, s) : cd{c.re * s.re, c.re * s.im};
+        g[2 * i] = v.re;
+        g[2 * i + 1] = v.im;
+    }
+    host_fft_pow2(g, N);
+    std::vector<float> G(2 * N);
+    for (size_t k1 = 0; k1 < N1; ++k1)
+        for (size_t k2 = 0; k2 < N2; ++k2) {
+            const size_t k = k1 + N1 * k2, o = k1 * N2 + k2;
+            G[2 * o] = (float)(g[2 * k] / (double)N);
+            G[2 * o + 1] = (float)(g[2 * k + 1] / (double)N);
+        }
+    std::vector<float> tw(2 * (N1 + N2));
+    for (size_t m = 0; m < N1 + N2; ++m) {
+        const double a = m < N1 ? -2.0 * M_PI * (double)m / (double)N1 : -2.0 * M_PI * (double)(m - N1) / (double)N2;
+        tw[2 * m] = (float)std::cos(a);
+        tw[2 * m + 1] = (float)std::sin(a);
+    }
+    SDSP_TRY(h->d_lG.ensure(G.size() * 4), "alloc long spectrum");
+    SDSP_TRY(h->d_ltw.ensure(tw.size() * 4), "alloc long tables");
+    SDSP_TRY(hipMemcpyAsync(h->d_lG.p, G.data(), G.size() * 4, hipMemcpyHostToDevice, h->stream), "copy long spectrum");
+    SDSP_TRY(hipMemcpyAsync(h->d_ltw.p, tw.data(), tw.size() * 4, hipMemcpyHostToDevice, h->stream),
+             "copy long tables");
+    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
+    h->olsl = OlsLongPlan{};
+    h->olsl.d_G = h->d_lG.p;
+    h->olsl.d_tw1 = h->d_ltw.p;
+    h->olsl.d_tw2 = (const float*)h->d_ltw.p + 2 * N1;
+    h->olsl.log2n = lg;
+    h->olsl.Lm1 = (int)(L - 1);
+    h->ols_ok = true;
+    return SDSP_OK;
+}
+
+// segments per round of the long path: the tuned value, else what 256 MiB of scratch hold
+size_t ols_long_round(const sdsp_fir* h, int lg) {
+    if (h->long_segs) return (size_t)h->long_segs;
+    const size_t s = ((size_t)256 << 20) / (((size_t)1 << lg) * 8);
+    return s ? s : 1;
 }
 
 // spectrum of g[i] = scale * h[L-1-i] in the lane layout of kern_fir_ols.hip
 int ols_build(sdsp_fir* h) {
+    if (ols_long(h)) return ols_long_build(h);
     SDSP_TRY(h->fence.wait(), "wait for queued work");
     const int N = kOlsN;
     const size_t L = h->L;
@@ -300,7 +377,8 @@ int fir_resolve_algo(const sdsp_fir* h, size_t n) {
     if (h->algo != SDSP_ALGO_AUTO) return h->algo;
     // AUTO: overlap-save for long 32-bit complex blocks, reference-order direct form otherwise
     // (real f32 streams take overlap-save only when asked: AUTO keeps their bits)
-    if (ols_applicable(h) && !ols_real(h) && n >= (size_t)(1 << 16)) return SDSP_ALGO_FFT;
+    if (ols_short(h) && !ols_real(h) && n >= (size_t)(1 << 16)) return SDSP_ALGO_FFT;
+    if (ols_long(h) && n >= kOlsLongAutoMin) return SDSP_ALGO_FFT;
     return SDSP_ALGO_EXACT;
 }
 // AUTO on a decimating handle: the fused multiply-add kernels for long 32-bit blocks (n inputs)
@@ -588,7 +666,8 @@ int sdsp_fir_set_channels(sdsp_fir* h, size_t channels) {
 int sdsp_fir_set_algo(sdsp_fir* h, int algo) {
     if (!h || algo < 0 || algo > 3) return SDSP_E_INVALID_ARGUMENT;
     if (algo == SDSP_ALGO_FFT && !ols_applicable(h)) {
-        set_error("overlap-save needs 32-bit samples (complex, or real with real taps), no decimation and L-1 <= 3840");
+        set_error("overlap-save needs no decimation and 32-bit samples: complex with L-1 <= 2^20, or real with real "
+                  "taps and L-1 <= 3840");
         return SDSP_E_UNSUPPORTED;
     }
     h->algo = algo;
@@ -615,6 +694,24 @@ int sdsp_fir_set_tuning(sdsp_fir* h, int key, int value) {
             if (value < kOlsOneShot || value > kOlsOneShotWide) return SDSP_E_INVALID_ARGUMENT;
             h->ols_kernel = value;
             h->ols.kernel = value;
+            return SDSP_OK;
+        case SDSP_TUNE_OLS_LONG_LOG2N:  // 0, or log2 N with 2^13 <= N <= 2^22 and N >= 2 (L-1) (long scope only)
+            if (value != 0 && !(ols_long(h) && value >= kOlsLongMinLog2N && value <= kOlsLongMaxLog2N &&
+                                ((size_t)1 << value) >= 2 * (h->L - 1))) {
+                set_error("long overlap-save transform size: 0, or log2 N in [13, 22] with N >= 2 (L-1) on a handle "
+                          "with 3840 < L-1 <= 2^20 and 32-bit complex samples");
+                return SDSP_E_INVALID_ARGUMENT;
+            }
+            if (value != h->long_log2n) {  // the plan is rebuilt on the next run
+                DeviceGuard g(h->device);
+                SDSP_TRY(h->fence.wait(), "wait for queued work");
+                h->long_log2n = value;
+                if (ols_long(h)) h->ols_ok = false;
+            }
+            return SDSP_OK;
+        case SDSP_TUNE_OLS_LONG_SEGS:
+            if (value < 0 || value > 4096) return SDSP_E_INVALID_ARGUMENT;
+            h->long_segs = value;
             return SDSP_OK;
         case SDSP_TUNE_DECIM_SEG:
             if (value < 0) return SDSP_E_INVALID_ARGUMENT;
@@ -651,6 +748,8 @@ int sdsp_fir_clone(const sdsp_fir* h, sdsp_fir** out) {
         if (st) return st;
     }
     c->ols_kernel = h->ols_kernel;
+    c->long_log2n = h->long_log2n;  // (the plan itself is rebuilt on the clone's first run)
+    c->long_segs = h->long_segs;
     c->decim_seg = h->decim_seg;
     const size_t hb = h->channels * (h->L - 1) * sample_bytes(h->dtype);
     st = h->quiesce();
@@ -675,6 +774,18 @@ int sdsp_fir_set_scale(sdsp_fir* h, const void* scale) {
 int sdsp_fir_get_scale(const sdsp_fir* h, void* scale) {
     if (!h || !scale) return SDSP_E_INVALID_ARGUMENT;
     std::memcpy(scale, h->scale.data(), h->scale.size());
+    return SDSP_OK;
+}
+int sdsp_fir_ols_info(const sdsp_fir* h, size_t* nfft, size_t* valid) {
+    if (!h || !nfft || !valid) return SDSP_E_INVALID_ARGUMENT;
+    *nfft = *valid = 0;
+    if (ols_short(h)) {
+        *nfft = kOlsN;
+        *valid = kOlsN - 256 * ((h->L - 1 + 255) / 256);
+    } else if (ols_long(h)) {
+        *nfft = (size_t)1 << ols_long_log2n(h);
+        *valid = *nfft - (h->L - 1);
+    }
     return SDSP_OK;
 }
 size_t sdsp_fir_len(const sdsp_fir* h) { return h ? h->L : 0; }
@@ -723,9 +834,18 @@ int sdsp_fir_execute_block_device(sdsp_fir* h, const void* d_in, size_t n, void*
                 int st = ols_build(h);
                 if (st) return st;
             }
-            SDSP_TRY(launch_fir_ols(h->ols, d_in, hist, h->hist.back(), d_out, n, (int)h->L, h->channels,
-                                    h->cus, s, &hist_done),
-                     "fir ols");
+            if (ols_long(h)) {
+                const int lg = h->olsl.log2n;
+                const size_t total = h->channels * ols_long_segments(n, lg, (int)h->L - 1);
+                const size_t round = std::min(total, ols_long_round(h, lg));
+                SDSP_TRY(h->d_ltmp.ensure(round * ((size_t)8 << lg)), "alloc long scratch");
+                SDSP_TRY(launch_fir_ols_long(h->olsl, d_in, hist, d_out, h->d_ltmp.p, n, h->channels, round, s),
+                         "fir ols long");
+            } else {
+                SDSP_TRY(launch_fir_ols(h->ols, d_in, hist, h->hist.back(), d_out, n, (int)h->L, h->channels,
+                                        h->cus, s, &hist_done),
+                         "fir ols");
+            }
         } else {
             FirArgs a{d_in, hist, h->d_taps_rev.p, h->scale.data(), d_out, n, n, h->channels, (int)h->L, 1, 0,
                       algo != SDSP_ALGO_FMA};

@@ -22,6 +22,10 @@ cd poly_response(const std::vector<cd>& c, bool real, double f);
 int fir_group_delay(const std::vector<cd>& h, bool real, double f, double* out);
 int iir_group_delay(const std::vector<double>& b, const std::vector<double>& a, double f, double* out);
 
+// in-place radix-2 FFT of M (a power of two) interleaved complex f64 values, forward sign
+// (runtime_fft.cpp)
+void host_fft_pow2(std::vector<double>& a, size_t M);
+
 void set_error(const std::string& msg);
 // the algorithm new FIR-type and IIR handles start on (sdsp_set_default_algo; SDSP_DEFAULT_ALGO)
 int default_algo();

@@ -72,6 +72,24 @@ hipError_t launch_fir_ols_real(const OlsPlan& p, const void* x, const void* hist
 hipError_t launch_fir_ols_pk(const OlsPlan& p, const void* x, void* y, size_t n, size_t channels, hipStream_t s,
                              long long lo, long long hi);
 
+// overlap-save for long filters on c32 samples (kern_fir_ols_long.hip): one transform of
+// N = 2^log2n = N1 N2 points per N - (L-1) outputs, N1 = 2^(log2n / 2), in three passes
+constexpr int kOlsLongMinLog2N = 13, kOlsLongMaxLog2N = 22;
+constexpr size_t kOlsLongMaxLm1 = (size_t)1 << 20;
+struct OlsLongPlan {
+    const void* d_G = nullptr;    // [N1][N2] c32: G[k1 + N1 k2] * scale / N (runtime.cpp ols_long_build)
+    const void* d_tw1 = nullptr;  // [N1] c32 e^{-j 2 pi m / N1}
+    const void* d_tw2 = nullptr;  // [N2] c32 e^{-j 2 pi m / N2}
+    int log2n = 0;
+    int Lm1 = 0;
+};
+// segments of one channel's block of n samples
+size_t ols_long_segments(size_t n, int log2n, int Lm1);
+// tmp: min(segs_per_round, channels * segments) * N c32 samples of scratch; a call with more
+// segments runs in rounds.  Writes y only; the caller runs the history update.
+hipError_t launch_fir_ols_long(const OlsLongPlan& p, const void* x, const void* hist, void* y, void* tmp, size_t n,
+                               size_t channels, size_t segs_per_round, hipStream_t s);
+
 // polyphase filterbank / interpolator: out[j*M + p] = sum_{i<K} cb[p*K + i] * ext(j - i)
 struct PfbArgs {
     const void* x;

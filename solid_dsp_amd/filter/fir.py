@@ -88,6 +88,13 @@ class _FirBase:
         """kernel-variant knobs (SDSP_TUNE_*, include/sdsp.h): performance only"""
         L.check(L.lib().sdsp_fir_set_tuning(self._h, int(key), int(value)))
 
+    def ols_info(self):
+        """(nfft, valid): segment transform size and outputs per segment ALGO_FFT would use on
+        this handle, (0, 0) where overlap-save does not apply (sdsp_fir_ols_info)"""
+        nfft, valid = C.c_size_t(0), C.c_size_t(0)
+        L.check(L.lib().sdsp_fir_ols_info(self._h, C.byref(nfft), C.byref(valid)))
+        return nfft.value, valid.value
+
     def set_host_step(self, on: bool, block_macs: int = None):
         """execute(sample), push and host blocks of n * len <= block_macs multiply-adds on the host
         against the handle's delay line (True, the default) or as device launches (False)."""
