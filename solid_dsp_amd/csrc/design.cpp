@@ -170,6 +170,35 @@ int iir_group_delay(const std::vector<double>& b, const std::vector<double>& a, 
     return 0;
 }
 
+// iterative radix-2 FFT in f64 on the host (Bluestein filter spectrum, long overlap-save
+// filter spectrum; plan time only)
+void host_fft_pow2(std::vector<double>& a, size_t M) {
+    for (size_t i = 1, j = 0; i < M; ++i) {
+        size_t bit = M >> 1;
+        for (; j & bit; bit >>= 1) j ^= bit;
+        j ^= bit;
+        if (i < j) {
+            std::swap(a[2 * i], a[2 * j]);
+            std::swap(a[2 * i + 1], a[2 * j + 1]);
+        }
+    }
+    for (size_t len = 2; len <= M; len <<= 1) {
+        for (size_t k = 0; k < len / 2; ++k) {
+            const double ang = -2.0 * M_PI * (double)k / (double)len;
+            const double wr = std::cos(ang), wi = std::sin(ang);
+            for (size_t i = 0; i < M; i += len) {
+                double* u = &a[2 * (i + k)];
+                double* v = &a[2 * (i + k + len / 2)];
+                const double tr = v[0] * wr - v[1] * wi, ti = v[0] * wi + v[1] * wr;
+                v[0] = u[0] - tr;
+                v[1] = u[1] - ti;
+                u[0] += tr;
+                u[1] += ti;
+            }
+        }
+    }
+}
+
 }  // namespace sdsp
 
 using namespace sdsp;

@@ -19,7 +19,7 @@
 // consecutive samples.  The inter-pass twiddles W_N^(+-a b) come from f64 sincospi of the exact
 // phase, as in fft_pass_kernel (kern_fft.hip); the N1- and N2-point transforms are the LDS
 // Stockham passes of sdsp_fft_dev.hpp with f64-computed tables.  The spectrum G holds
-// scale / N (runtime.cpp ols_long_build).  Channels are folded into the segment index.
+// scale / N (ols_tables.cpp ols_long_spectrum).  Channels are folded into the segment index.
 #include "sdsp_device.hpp"
 #include "sdsp_fft_dev.hpp"
 #include "sdsp_kernels.hpp"

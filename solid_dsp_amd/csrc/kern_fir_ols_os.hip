@@ -82,7 +82,7 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
     const auto rx = __builtin_amdgcn_make_buffer_rsrc((void*)xw, (short)0, nrec, kBufWord3);
     const auto ry = __builtin_amdgcn_make_buffer_rsrc((void*)yw, (short)0, nrec, kBufWord3);
     const auto rt = __builtin_amdgcn_make_buffer_rsrc((void*)tb, (short)0, kOlsOsTabF4 * 16, kBufWord3);
-    // twiddle bases: {C1, D1} of column t and {E1, F1} of row lo4 (runtime.cpp ols_build), requested
+    // twiddle bases: {C1, D1} of column t and {E1, F1} of row lo4 (ols_tables.cpp ols_os_bases), requested
     // before the segment's rows (L2 hits that land while the rows stream in)
     const float4 cd = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rt, 16 * t, 16 * kOlsOsTabCD, 0));
     const float4 ef = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rt, 16 * lo4, 16 * kOlsOsTabEF, 0));

@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "ols_tables.hpp"
 #include "sdsp.h"
 #include "sdsp_host.hpp"
 #include "sdsp_kernels.hpp"
@@ -81,6 +82,37 @@ using namespace sdsp;
 // ===========================================================================
 // FIR / decimating FIR
 // ===========================================================================
+struct sdsp_fir;
+
+// The overlap-save side of a FIR handle: which plan applies, the device tables (contents:
+// ols_tables.cpp), the long path's scratch, the two launch plans, the knobs, and whether the
+// tables match the handle's taps, scale and transform size.  Defined below sdsp_fir.
+struct FirOls {
+    bool ok = false;     // false: the next run builds the tables first
+    OlsPlan plan{};      // 4096-point kernels; plan.kernel is SDSP_TUNE_OLS_KERNEL (build leaves it alone)
+    OlsLongPlan lplan{};  // three-pass path of kern_fir_ols_long.hip (L - 1 > 3840, c32 samples)
+    int long_log2n = 0;  // SDSP_TUNE_OLS_LONG_LOG2N (0 = automatic)
+    int long_segs = 0;   // SDSP_TUNE_OLS_LONG_SEGS (0 = automatic)
+    DevBuf H, tw1, tw2, pkt, ostab, hhalf;
+    DevBuf lG, ltw, ltmp;  // spectrum [N1][N2], tables [N1 | N2], scratch [segments][N]
+
+    static bool is_real(const sdsp_fir* h);   // real f32 samples and taps: kern_fir_ols_real.hip
+    static bool is_short(const sdsp_fir* h);  // the 4096-point one-workgroup segment kernels
+    static bool is_long(const sdsp_fir* h);   // longer taps on c32 samples: the three-pass transform
+    static bool applicable(const sdsp_fir* h) { return is_short(h) || is_long(h); }
+    int log2n(const sdsp_fir* h) const;       // of the long path's transform size
+    void info(const sdsp_fir* h, size_t* nfft, size_t* valid) const;
+    void invalidate() { ok = false; }
+    int build(sdsp_fir* h);
+    // one block on stream s (builds first when the tables are stale); *hist_done as launch_fir_ols
+    int run(sdsp_fir* h, const void* d_in, const void* hist, void* d_out, size_t n, hipStream_t s, bool* hist_done);
+    void copy_knobs_from(const FirOls& o) {  // a clone builds its own tables on its first run
+        plan.kernel = o.plan.kernel;
+        long_log2n = o.long_log2n;
+        long_segs = o.long_segs;
+    }
+};
+
 struct sdsp_fir : HandleCore {
     int dtype = 0, cus = 256;
     mutable unsigned long long device_ops = 0;  // sdsp_fir_device_ops
@@ -101,18 +133,106 @@ struct sdsp_fir : HandleCore {
     bool dev_stale = false;   // the host consumed samples after hist.front() was last written
     int host_step = 1;        // SDSP_TUNE_HOST_STEP
     size_t host_macs = 1u << 16;  // host blocks: n * L up to this many multiply-adds
-    // overlap-save plan
-    bool ols_ok = false;
-    int ols_kernel = kOlsOneShot;  // SDSP_TUNE_OLS_KERNEL
     int decim_seg = 0;  // outputs per lane group of the polyphase decimator (0 = auto)
-    OlsPlan ols{};
-    DevBuf d_H, d_tw1, d_tw2, d_pkt, d_ostab, d_hhalf;
-    // long filters (L - 1 > 3840, c32 samples): the three-pass plan of kern_fir_ols_long.hip
-    int long_log2n = 0;  // SDSP_TUNE_OLS_LONG_LOG2N (0 = automatic)
-    int long_segs = 0;   // SDSP_TUNE_OLS_LONG_SEGS (0 = automatic)
-    OlsLongPlan olsl{};
-    DevBuf d_lG, d_ltw, d_ltmp;  // spectrum [N1][N2], tables [N1 | N2], scratch [segments][N]
+    FirOls ols;         // overlap-save plan
 };
+
+bool FirOls::is_real(const sdsp_fir* h) { return h->dtype == SDSP_RR32; }
+bool FirOls::is_short(const sdsp_fir* h) {
+    return (h->dtype == SDSP_RR32 || h->dtype == SDSP_RC32 || h->dtype == SDSP_CC32) && h->M == 1 && h->L >= 2 &&
+           h->L - 1 <= 256 * 15;
+}
+bool FirOls::is_long(const sdsp_fir* h) {
+    return (h->dtype == SDSP_RC32 || h->dtype == SDSP_CC32) && h->M == 1 && h->L - 1 > 256 * 15 &&
+           h->L - 1 <= kOlsLongMaxLm1;
+}
+
+// the tuned value, else the smallest power of two >= 4 (L-1) and >= 2^14 (at least three
+// quarters of every transform is output)
+int FirOls::log2n(const sdsp_fir* h) const {
+    if (long_log2n) return long_log2n;
+    int lg = 14;
+    while (((size_t)1 << lg) < 4 * (h->L - 1)) ++lg;
+    return lg;
+}
+
+void FirOls::info(const sdsp_fir* h, size_t* nfft, size_t* valid) const {
+    *nfft = *valid = 0;
+    if (is_short(h)) {
+        *nfft = kOlsN;
+        *valid = kOlsN - 256 * ((h->L - 1 + 255) / 256);
+    } else if (is_long(h)) {
+        *nfft = (size_t)1 << log2n(h);
+        *valid = *nfft - (h->L - 1);
+    }
+}
+
+// one table into its device buffer, queued on s: `v` must live until s is synchronised
+static int upload(DevBuf& b, const std::vector<float>& v, hipStream_t s, const char* what) {
+    SDSP_TRY(b.ensure(v.size() * 4), std::string("alloc ").append(what).c_str());
+    SDSP_TRY(hipMemcpyAsync(b.p, v.data(), v.size() * 4, hipMemcpyHostToDevice, s),
+             std::string("copy ").append(what).c_str());
+    return SDSP_OK;
+}
+
+// tables of g[i] = scale * h[L-1-i] on the device (ols_tables.cpp), and the plan that points at them
+int FirOls::build(sdsp_fir* h) {
+    SDSP_TRY(h->fence.wait(), "wait for queued work");
+    const unsigned char *taps = h->taps.data(), *scale = h->scale.data();
+    hipStream_t s = h->stream;
+    int st = SDSP_OK;
+    if (is_long(h)) {
+        const int lg = log2n(h);
+        const std::vector<float> G = ols_long_spectrum(taps, scale, h->dtype, h->L, lg), tw = ols_long_twiddles(lg);
+        if ((st = upload(lG, G, s, "long spectrum")) || (st = upload(ltw, tw, s, "long tables"))) return st;
+        SDSP_TRY(hipStreamSynchronize(s), "sync");
+        const size_t N1 = (size_t)1 << (lg / 2);
+        lplan = OlsLongPlan{lG.p, ltw.p, (const float*)ltw.p + 2 * N1, lg, (int)(h->L - 1)};
+        ok = true;
+        return SDSP_OK;
+    }
+    const std::vector<cd> G = ols_spectrum(taps, scale, h->dtype, h->L);
+    const std::vector<float> Hs = ols_rows_H(G), t1 = ols_rows_tw(256, 4096), t2 = ols_rows_tw(16, 256);
+    const std::vector<float> pk = ols_pack_pkt(Hs, t1, t2), os = ols_os_bases();
+    // real f32 samples: the packed-pair kernel reads pkt and ostab only (H, tw1, tw2 stay null)
+    const bool real = is_real(h), real_taps = ols_real_taps(h->dtype, scale);
+    const std::vector<float> hh = real_taps ? ols_half_table(G) : std::vector<float>();
+    if (!real && ((st = upload(H, Hs, s, "H")) || (st = upload(tw1, t1, s, "tw1")) || (st = upload(tw2, t2, s, "tw2"))))
+        return st;
+    if ((st = upload(pkt, pk, s, "packed tables")) || (st = upload(ostab, os, s, "one-shot tables"))) return st;
+    if (real_taps && (st = upload(hhalf, hh, s, "half spectrum"))) return st;
+    SDSP_TRY(hipStreamSynchronize(s), "sync");
+    plan.d_H = H.p;
+    plan.d_tw1 = tw1.p;
+    plan.d_tw2 = tw2.p;
+    plan.d_pkt = pkt.p;
+    plan.d_ostab = ostab.p;
+    plan.d_hhalf = real_taps ? hhalf.p : nullptr;
+    plan.sample_bytes = real ? 4 : 8;
+    plan.halo_rows = (int)((h->L - 1 + 255) / 256);
+    ok = true;
+    return SDSP_OK;
+}
+
+int FirOls::run(sdsp_fir* h, const void* d_in, const void* hist, void* d_out, size_t n, hipStream_t s,
+                bool* hist_done) {
+    if (!ok)
+        if (int st = build(h)) return st;
+    if (!is_long(h)) {
+        SDSP_TRY(launch_fir_ols(plan, d_in, hist, h->hist.back(), d_out, n, (int)h->L, h->channels, h->cus, s,
+                                hist_done),
+                 "fir ols");
+        return SDSP_OK;
+    }
+    const int lg = lplan.log2n;
+    const size_t total = h->channels * ols_long_segments(n, lg, (int)h->L - 1);
+    // segments per round: the tuned value, else what 256 MiB of scratch hold
+    const size_t fit = std::max<size_t>(1, ((size_t)256 << 20) / ((size_t)8 << lg));
+    const size_t round = std::min(total, long_segs ? (size_t)long_segs : fit);
+    SDSP_TRY(ltmp.ensure(round * ((size_t)8 << lg)), "alloc long scratch");
+    SDSP_TRY(launch_fir_ols_long(lplan, d_in, hist, d_out, ltmp.p, n, h->channels, round, s), "fir ols long");
+    return SDSP_OK;
+}
 
 namespace {
 
@@ -129,256 +249,17 @@ int fir_alloc_state(sdsp_fir* h) {
     return SDSP_OK;
 }
 
-// real f32 samples with real f32 taps run the packed-pair kernel (kern_fir_ols_real.hip)
-bool ols_real(const sdsp_fir* h) { return h->dtype == SDSP_RR32; }
-
-// the 4096-point one-workgroup segment kernels
-bool ols_short(const sdsp_fir* h) {
-    return (h->dtype == SDSP_RR32 || h->dtype == SDSP_RC32 || h->dtype == SDSP_CC32) && h->M == 1 && h->L >= 2 &&
-           h->L - 1 <= 256 * 15;
-}
-// longer taps on c32 samples: the three-pass segment transform (kern_fir_ols_long.hip)
-bool ols_long(const sdsp_fir* h) {
-    return (h->dtype == SDSP_RC32 || h->dtype == SDSP_CC32) && h->M == 1 && h->L - 1 > 256 * 15 &&
-           h->L - 1 <= kOlsLongMaxLm1;
-}
-bool ols_applicable(const sdsp_fir* h) { return ols_short(h) || ols_long(h); }
-
 // AUTO moves a long-filter c32 block to the three-pass path from this many samples
 // (profiles/r10/LAB.md: the A/B against the reference-order kernel at L = 3842)
 constexpr size_t kOlsLongAutoMin = (size_t)1 << 16;
 
-// log2 of the long path's transform size: the tuned value, else the smallest power of two
-// >= 4 (L-1) and >= 2^14 (at least three quarters of every transform is output)
-int ols_long_log2n(const sdsp_fir* h) {
-    if (h->long_log2n) return h->long_log2n;
-    int lg = 14;
-    while (((size_t)1 << lg) < 4 * (h->L - 1)) ++lg;
-    return lg;
-}
-
-// spectrum of g[i] = scale * h[L-1-i], zero-padded to N, over N, in [k1][k2] order
-// (k = k1 + N1 k2), and the tables of the N1- and N2-point transforms
-int ols_long_build(sdsp_fir* h) {
-    SDSP_TRY(h->fence.wait(), "wait for queued work");
-    const int lg = ols_long_log2n(h), l1 = lg / 2, l2 = lg - l1;
-    const size_t N = (size_t)1 << lg, N1 = (size_t)1 << l1, N2 = (size_t)1 << l2, L = h->L;
-    std::vector<double> g(2 * N, 0.0);
-    const cd s = coef_at(h->scale.data(), h->dtype, 0);
-    for (size_t i = 0; i < L; ++i) {
-        const cd c = coef_at(h->taps.data(), h->dtype, L - 1 - i);
-        const cd v = coef_is_complex(h->dtype) ? cmul(c, s) : cd{c.re * s.re, c.re * s.im};
-        g[2 * i] = v.re;
-        g[2 * i + 1] = v.im;
-    }
-    host_fft_pow2(g, N);
-    std::vector<float> G(2 * N);
-    for (size_t k1 = 0; k1 < N1; ++k1)
-        for (size_t k2 = 0; k2 < N2; ++k2) {
-            const size_t k = k1 + N1 * k2, o = k1 * N2 + k2;
-            G[2 * o] = (float)(g[2 * k] / (double)N);
-            G[2 * o + 1] = (float)(g[2 * k + 1] / (double)N);
-        }
-    std::vector<float> tw(2 * (N1 + N2));
-    for (size_t m = 0; m < N1 + N2; ++m) {
-        const double a = m < N1 ? -2.0 * M_PI * (double)m / (double)N1 : -2.0 * M_PI * (double)(m - N1) / (double)N2;
-        tw[2 * m] = (float)std::cos(a);
-        tw[2 * m + 1] = (float)std::sin(a);
-    }
-    SDSP_TRY(h->d_lG.ensure(G.size() * 4), "alloc long spectrum");
-    SDSP_TRY(h->d_ltw.ensure(tw.size() * 4), "alloc long tables");
-    SDSP_TRY(hipMemcpyAsync(h->d_lG.p, G.data(), G.size() * 4, hipMemcpyHostToDevice, h->stream), "copy long spectrum");
-    SDSP_TRY(hipMemcpyAsync(h->d_ltw.p, tw.data(), tw.size() * 4, hipMemcpyHostToDevice, h->stream),
-             "copy long tables");
-    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
-    h->olsl = OlsLongPlan{};
-    h->olsl.d_G = h->d_lG.p;
-    h->olsl.d_tw1 = h->d_ltw.p;
-    h->olsl.d_tw2 = (const float*)h->d_ltw.p + 2 * N1;
-    h->olsl.log2n = lg;
-    h->olsl.Lm1 = (int)(L - 1);
-    h->ols_ok = true;
-    return SDSP_OK;
-}
-
-// segments per round of the long path: the tuned value, else what 256 MiB of scratch hold
-size_t ols_long_round(const sdsp_fir* h, int lg) {
-    if (h->long_segs) return (size_t)h->long_segs;
-    const size_t s = ((size_t)256 << 20) / (((size_t)1 << lg) * 8);
-    return s ? s : 1;
-}
-
-// spectrum of g[i] = scale * h[L-1-i] in the lane layout of kern_fir_ols.hip
-int ols_build(sdsp_fir* h) {
-    if (ols_long(h)) return ols_long_build(h);
-    SDSP_TRY(h->fence.wait(), "wait for queued work");
-    const int N = kOlsN;
-    const size_t L = h->L;
-    const int h2 = (int)((L - 1 + 255) / 256);
-    std::vector<cd> g(N, cd{0.0, 0.0});
-    const cd s = coef_at(h->scale.data(), h->dtype, 0);
-    for (size_t i = 0; i < L; ++i) {
-        cd c = coef_at(h->taps.data(), h->dtype, L - 1 - i);
-        g[i] = coef_is_complex(h->dtype) ? cmul(c, s) : cd{c.re * s.re, c.re * s.im};
-    }
-    // direct DFT in f64 (one-time, O(N L))
-    std::vector<cd> G(N);
-    const double w = -2.0 * M_PI / N;
-    for (int k = 0; k < N; ++k) {
-        double re = 0.0, im = 0.0;
-        for (size_t i = 0; i < L; ++i) {
-            const long long ph = ((long long)i * k) % N;
-            const double c = std::cos(w * (double)ph), sn = std::sin(w * (double)ph);
-            re += g[i].re * c - g[i].im * sn;
-            im += g[i].re * sn + g[i].im * c;
-        }
-        G[k] = {re / N, im / N};
-    }
-    // real taps, real scale, complex samples: g is real, so its spectrum is conjugate-symmetric.
-    // The sums above are so only to rounding; the symmetry is made exact here, before anything is
-    // rounded to f32 or packed, so that the full tables and the half table hold the same values
-    // and every kernel computes the same bits from either (kern_fir_ols_os.hip REALG)
-    const bool real_taps = !coef_is_complex(h->dtype) && !ols_real(h) && s.im == 0.0;
-    if (real_taps) {
-        for (int k = 1; k < N / 2; ++k) G[N - k] = cd{G[k].re, -G[k].im};
-        G[0].im = 0.0;
-        G[N / 2].im = 0.0;
-    }
-    std::vector<float> Hs(2 * 4096), tw1(2 * 4096), tw2(2 * 256);
-    for (int t = 0; t < 256; ++t) {
-        const int k0 = t >> 4, k1 = t & 15;
-        for (int k2 = 0; k2 < 16; ++k2) {
-            const cd v = G[k0 + 16 * k1 + 256 * k2];
-            Hs[2 * (t * 16 + k2)] = (float)v.re;
-            Hs[2 * (t * 16 + k2) + 1] = (float)v.im;
-        }
-        for (int k = 0; k < 16; ++k) {
-            const long long ph = ((long long)t * k) % 4096;
-            tw1[2 * (t * 16 + k)] = (float)std::cos(-2.0 * M_PI * ph / 4096.0);
-            tw1[2 * (t * 16 + k) + 1] = (float)std::sin(-2.0 * M_PI * ph / 4096.0);
-        }
-    }
-    for (int a = 0; a < 16; ++a)
-        for (int b = 0; b < 16; ++b) {
-            const int ph = (a * b) % 256;
-            tw2[2 * (a * 16 + b)] = (float)std::cos(-2.0 * M_PI * ph / 256.0);
-            tw2[2 * (a * 16 + b) + 1] = (float)std::sin(-2.0 * M_PI * ph / 256.0);
-        }
-    // real f32 samples: the packed-pair kernel reads d_pkt and d_ostab only
-    const bool real = ols_real(h);
-    if (!real) {
-        SDSP_TRY(h->d_H.ensure(Hs.size() * 4), "alloc H");
-        SDSP_TRY(h->d_tw1.ensure(tw1.size() * 4), "alloc tw1");
-        SDSP_TRY(h->d_tw2.ensure(tw2.size() * 4), "alloc tw2");
-        SDSP_TRY(hipMemcpyAsync(h->d_H.p, Hs.data(), Hs.size() * 4, hipMemcpyHostToDevice, h->stream), "copy H");
-        SDSP_TRY(hipMemcpyAsync(h->d_tw1.p, tw1.data(), tw1.size() * 4, hipMemcpyHostToDevice, h->stream),
-                 "copy tw1");
-        SDSP_TRY(hipMemcpyAsync(h->d_tw2.p, tw2.data(), tw2.size() * 4, hipMemcpyHostToDevice, h->stream),
-                 "copy tw2");
-    }
-    // the same tables for the packed kernel, k-pair major so that a table load is one
-    // coalesced 16-byte access per lane: float4 (p, i) = entries 2p, 2p + 1 of row i;
-    // [0, 2048): H rows t, [2048, 4096): tw1 rows, [4096, 4224): tw2 rows
-    std::vector<float> pkt(4 * 4224);
-    for (int q = 0; q < 8; ++q) {
-        for (int i = 0; i < 256; ++i)
-            for (int e = 0; e < 4; ++e) {
-                pkt[4 * (q * 256 + i) + e] = Hs[2 * (i * 16 + 2 * q) + e];
-                pkt[4 * (2048 + q * 256 + i) + e] = tw1[2 * (i * 16 + 2 * q) + e];
-            }
-        for (int i = 0; i < 16; ++i)
-            for (int e = 0; e < 4; ++e) pkt[4 * (4096 + q * 16 + i) + e] = tw2[2 * (i * 16 + 2 * q) + e];
-    }
-    SDSP_TRY(h->d_pkt.ensure(pkt.size() * 4), "alloc packed tables");
-    SDSP_TRY(hipMemcpyAsync(h->d_pkt.p, pkt.data(), pkt.size() * 4, hipMemcpyHostToDevice, h->stream),
-             "copy packed tables");
-    // one-shot kernel (kern_fir_ols_os.hip): per column c the twiddle bases C_b = W4096^(b c),
-    // D_a = W4096^(4 a c) (b, a = 1..3) as float4 [q][c] = (C1 C2 | C3 D1 | D2 D3), then per
-    // row l the W256 bases E_b = W256^(b l), F_a = W256^(4 a l) as float4 [768 + 16 q + l], then
-    // the first powers alone (kOlsOsTabCD, kOlsOsTabEF: the default kernel's two loads)
-    std::vector<float> os(4 * kOlsOsTabF4);
-    auto put = [&](size_t f4, int half, long long m, int nn) {
-        const double ang = -2.0 * M_PI * (double)(m % nn) / nn;
-        os[4 * f4 + 2 * half] = (float)std::cos(ang);
-        os[4 * f4 + 2 * half + 1] = (float)std::sin(ang);
-    };
-    for (int c = 0; c < 256; ++c) {
-        put(c, 0, c, 4096);
-        put(c, 1, 2LL * c, 4096);
-        put(256 + c, 0, 3LL * c, 4096);
-        put(256 + c, 1, 4LL * c, 4096);
-        put(512 + c, 0, 8LL * c, 4096);
-        put(512 + c, 1, 12LL * c, 4096);
-    }
-    for (int c = 0; c < 256; ++c) {  // {C1, D1} per column
-        put(kOlsOsTabCD + c, 0, c, 4096);
-        put(kOlsOsTabCD + c, 1, 4LL * c, 4096);
-    }
-    for (int l = 0; l < 16; ++l) {  // {E1, F1} per row
-        put(kOlsOsTabEF + l, 0, l, 256);
-        put(kOlsOsTabEF + l, 1, 4LL * l, 256);
-    }
-    for (int l = 0; l < 16; ++l) {
-        put(768 + l, 0, l, 256);
-        put(768 + l, 1, 2LL * l, 256);
-        put(784 + l, 0, 3LL * l, 256);
-        put(784 + l, 1, 4LL * l, 256);
-        put(800 + l, 0, 8LL * l, 256);
-        put(800 + l, 1, 12LL * l, 256);
-    }
-    SDSP_TRY(h->d_ostab.ensure(os.size() * 4), "alloc one-shot tables");
-    SDSP_TRY(hipMemcpyAsync(h->d_ostab.p, os.data(), os.size() * 4, hipMemcpyHostToDevice, h->stream),
-             "copy one-shot tables");
-    // real taps: H[N - k] = conj(H[k]), so the one-shot kernel reads bins k2 < 8 of every lane from
-    // a half table and the others as the conjugates of its mirror lane's (kern_fir_ols_os.hip):
-    // float4 [p][i] = {H(i, 2p), H(i, 2p + 1)} for p < 4, H(i, k2) = G[k0 + 16 k1 + 256 k2] of
-    // lane i = 16 k0 + k1; entry i = 256 is the mirror of lane (0, 0), whose bins k2 >= 8 mirror
-    // k2' = 16 - k2 (k2' = 8 included): stored so that the kernel's conj-and-swap yields them
-    if (real_taps) {
-        std::vector<float> hh(4 * 4 * kOlsHalfRow);
-        auto set = [&](int q, int i, int half, cd v) {
-            hh[4 * (q * kOlsHalfRow + i) + 2 * half] = (float)v.re;
-            hh[4 * (q * kOlsHalfRow + i) + 2 * half + 1] = (float)v.im;
-        };
-        for (int q = 0; q < 4; ++q) {
-            for (int i = 0; i < 256; ++i) {
-                const int k0 = i >> 4, k1 = i & 15;
-                set(q, i, 0, G[k0 + 16 * k1 + 256 * (2 * q)]);
-                set(q, i, 1, G[k0 + 16 * k1 + 256 * (2 * q + 1)]);
-            }
-            // lane (0, 0), pair p = 7 - q of its bins k2 = 2p, 2p + 1: stored as
-            // {conj H(256 (2p + 1)), conj H(256 (2p))} at the mirror slot
-            const int pp = 7 - q;
-            const cd a = G[256 * (2 * pp + 1)], b = G[256 * (2 * pp)];
-            set(q, 256, 0, cd{a.re, -a.im});
-            set(q, 256, 1, cd{b.re, -b.im});
-        }
-        SDSP_TRY(h->d_hhalf.ensure(hh.size() * 4), "alloc half spectrum");
-        SDSP_TRY(hipMemcpyAsync(h->d_hhalf.p, hh.data(), hh.size() * 4, hipMemcpyHostToDevice, h->stream),
-                 "copy half spectrum");
-    }
-    SDSP_TRY(hipStreamSynchronize(h->stream), "sync");
-    h->ols = OlsPlan{};
-    h->ols.d_hhalf = real_taps ? h->d_hhalf.p : nullptr;
-    h->ols.d_H = real ? nullptr : h->d_H.p;
-    h->ols.d_tw1 = real ? nullptr : h->d_tw1.p;
-    h->ols.d_tw2 = real ? nullptr : h->d_tw2.p;
-    h->ols.sample_bytes = real ? 4 : 8;
-    h->ols.halo_rows = h2;
-    h->ols.kernel = h->ols_kernel;
-    h->ols.d_pkt = h->d_pkt.p;
-    h->ols.d_ostab = h->d_ostab.p;
-    h->ols_ok = true;
-    return SDSP_OK;
-}
-
 int fir_resolve_algo(const sdsp_fir* h, size_t n) {
-    if (h->algo == SDSP_ALGO_FFT) return ols_applicable(h) ? SDSP_ALGO_FFT : SDSP_ALGO_EXACT;
+    if (h->algo == SDSP_ALGO_FFT) return FirOls::applicable(h) ? SDSP_ALGO_FFT : SDSP_ALGO_EXACT;
     if (h->algo != SDSP_ALGO_AUTO) return h->algo;
     // AUTO: overlap-save for long 32-bit complex blocks, reference-order direct form otherwise
     // (real f32 streams take overlap-save only when asked: AUTO keeps their bits)
-    if (ols_short(h) && !ols_real(h) && n >= (size_t)(1 << 16)) return SDSP_ALGO_FFT;
-    if (ols_long(h) && n >= kOlsLongAutoMin) return SDSP_ALGO_FFT;
+    if (FirOls::is_short(h) && !FirOls::is_real(h) && n >= (size_t)(1 << 16)) return SDSP_ALGO_FFT;
+    if (FirOls::is_long(h) && n >= kOlsLongAutoMin) return SDSP_ALGO_FFT;
     return SDSP_ALGO_EXACT;
 }
 // AUTO on a decimating handle: the fused multiply-add kernels for long 32-bit blocks (n inputs)
@@ -438,9 +319,6 @@ int fir_create_common(sdsp_fir** out, int dtype, const void* taps, size_t len, c
     return SDSP_OK;
 }
 
-}  // namespace
-
-namespace {
 // ---------------------------------------------------------------------------
 // Host step: Filter::execute(sample), DecimatingFIRFilter::push and small host
 // blocks run on the host against the handle's own delay line, in
@@ -665,7 +543,7 @@ int sdsp_fir_set_channels(sdsp_fir* h, size_t channels) {
 
 int sdsp_fir_set_algo(sdsp_fir* h, int algo) {
     if (!h || algo < 0 || algo > 3) return SDSP_E_INVALID_ARGUMENT;
-    if (algo == SDSP_ALGO_FFT && !ols_applicable(h)) {
+    if (algo == SDSP_ALGO_FFT && !FirOls::applicable(h)) {
         set_error("overlap-save needs no decimation and 32-bit samples: complex with L-1 <= 2^20, or real with real "
                   "taps and L-1 <= 3840");
         return SDSP_E_UNSUPPORTED;
@@ -692,26 +570,25 @@ int sdsp_fir_set_tuning(sdsp_fir* h, int key, int value) {
     switch (key) {
         case SDSP_TUNE_OLS_KERNEL:  // every value computes the full output (performance only)
             if (value < kOlsOneShot || value > kOlsOneShotWide) return SDSP_E_INVALID_ARGUMENT;
-            h->ols_kernel = value;
-            h->ols.kernel = value;
+            h->ols.plan.kernel = value;
             return SDSP_OK;
         case SDSP_TUNE_OLS_LONG_LOG2N:  // 0, or log2 N with 2^13 <= N <= 2^22 and N >= 2 (L-1) (long scope only)
-            if (value != 0 && !(ols_long(h) && value >= kOlsLongMinLog2N && value <= kOlsLongMaxLog2N &&
+            if (value != 0 && !(FirOls::is_long(h) && value >= kOlsLongMinLog2N && value <= kOlsLongMaxLog2N &&
                                 ((size_t)1 << value) >= 2 * (h->L - 1))) {
                 set_error("long overlap-save transform size: 0, or log2 N in [13, 22] with N >= 2 (L-1) on a handle "
                           "with 3840 < L-1 <= 2^20 and 32-bit complex samples");
                 return SDSP_E_INVALID_ARGUMENT;
             }
-            if (value != h->long_log2n) {  // the plan is rebuilt on the next run
+            if (value != h->ols.long_log2n) {  // the plan is rebuilt on the next run
                 DeviceGuard g(h->device);
                 SDSP_TRY(h->fence.wait(), "wait for queued work");
-                h->long_log2n = value;
-                if (ols_long(h)) h->ols_ok = false;
+                h->ols.long_log2n = value;
+                if (FirOls::is_long(h)) h->ols.invalidate();
             }
             return SDSP_OK;
         case SDSP_TUNE_OLS_LONG_SEGS:
             if (value < 0 || value > 4096) return SDSP_E_INVALID_ARGUMENT;
-            h->long_segs = value;
+            h->ols.long_segs = value;
             return SDSP_OK;
         case SDSP_TUNE_DECIM_SEG:
             if (value < 0) return SDSP_E_INVALID_ARGUMENT;
@@ -747,9 +624,7 @@ int sdsp_fir_clone(const sdsp_fir* h, sdsp_fir** out) {
         st = sdsp_fir_set_channels(c, h->channels);
         if (st) return st;
     }
-    c->ols_kernel = h->ols_kernel;
-    c->long_log2n = h->long_log2n;  // (the plan itself is rebuilt on the clone's first run)
-    c->long_segs = h->long_segs;
+    c->ols.copy_knobs_from(h->ols);
     c->decim_seg = h->decim_seg;
     const size_t hb = h->channels * (h->L - 1) * sample_bytes(h->dtype);
     st = h->quiesce();
@@ -768,7 +643,7 @@ int sdsp_fir_set_scale(sdsp_fir* h, const void* scale) {
     DeviceGuard g(h->device);
     SDSP_TRY(h->fence.wait(), "wait for queued work");  // the next run rebuilds tables a queued kernel may read
     std::memcpy(h->scale.data(), scale, h->scale.size());
-    h->ols_ok = false;
+    h->ols.invalidate();
     return SDSP_OK;
 }
 int sdsp_fir_get_scale(const sdsp_fir* h, void* scale) {
@@ -778,14 +653,7 @@ int sdsp_fir_get_scale(const sdsp_fir* h, void* scale) {
 }
 int sdsp_fir_ols_info(const sdsp_fir* h, size_t* nfft, size_t* valid) {
     if (!h || !nfft || !valid) return SDSP_E_INVALID_ARGUMENT;
-    *nfft = *valid = 0;
-    if (ols_short(h)) {
-        *nfft = kOlsN;
-        *valid = kOlsN - 256 * ((h->L - 1 + 255) / 256);
-    } else if (ols_long(h)) {
-        *nfft = (size_t)1 << ols_long_log2n(h);
-        *valid = *nfft - (h->L - 1);
-    }
+    h->ols.info(h, nfft, valid);
     return SDSP_OK;
 }
 size_t sdsp_fir_len(const sdsp_fir* h) { return h ? h->L : 0; }
@@ -830,22 +698,7 @@ int sdsp_fir_execute_block_device(sdsp_fir* h, const void* d_in, size_t n, void*
     if (h->M == 1) {
         const int algo = fir_resolve_algo(h, n);
         if (algo == SDSP_ALGO_FFT) {
-            if (!h->ols_ok) {
-                int st = ols_build(h);
-                if (st) return st;
-            }
-            if (ols_long(h)) {
-                const int lg = h->olsl.log2n;
-                const size_t total = h->channels * ols_long_segments(n, lg, (int)h->L - 1);
-                const size_t round = std::min(total, ols_long_round(h, lg));
-                SDSP_TRY(h->d_ltmp.ensure(round * ((size_t)8 << lg)), "alloc long scratch");
-                SDSP_TRY(launch_fir_ols_long(h->olsl, d_in, hist, d_out, h->d_ltmp.p, n, h->channels, round, s),
-                         "fir ols long");
-            } else {
-                SDSP_TRY(launch_fir_ols(h->ols, d_in, hist, h->hist.back(), d_out, n, (int)h->L, h->channels,
-                                        h->cus, s, &hist_done),
-                         "fir ols");
-            }
+            if (int st = h->ols.run(h, d_in, hist, d_out, n, s, &hist_done)) return st;
         } else {
             FirArgs a{d_in, hist, h->d_taps_rev.p, h->scale.data(), d_out, n, n, h->channels, (int)h->L, 1, 0,
                       algo != SDSP_ALGO_FMA};

@@ -23,7 +23,7 @@ int fir_group_delay(const std::vector<cd>& h, bool real, double f, double* out);
 int iir_group_delay(const std::vector<double>& b, const std::vector<double>& a, double f, double* out);
 
 // in-place radix-2 FFT of M (a power of two) interleaved complex f64 values, forward sign
-// (runtime_fft.cpp)
+// (design.cpp)
 void host_fft_pow2(std::vector<double>& a, size_t M);
 
 void set_error(const std::string& msg);

@@ -35,7 +35,7 @@ constexpr int kOlsOneShotWide = 3;  // the one-shot kernel with 16-byte lanes (p
                                     // real f32: 8-byte lanes, every other value the 4-byte default
 constexpr int kOlsSegsPerBlock = 16;
 // W4096 column bases [3][256], W256 row bases [3][16], then the first powers alone: {C1, D1}
-// per column [256] and {E1, F1} per row [16] (kern_fir_ols_os.hip, runtime.cpp ols_build)
+// per column [256] and {E1, F1} per row [16] (kern_fir_ols_os.hip, ols_tables.cpp ols_os_bases)
 constexpr int kOlsOsTabCD = 768 + 48, kOlsOsTabEF = kOlsOsTabCD + 256;
 constexpr int kOlsOsTabF4 = kOlsOsTabEF + 16;
 
@@ -46,11 +46,11 @@ struct OlsPlan {
     int halo_rows;  // h2: halo = 256*h2 >= L-1
     int kernel = kOlsOneShot;
     void* d_pkt = nullptr;    // k-pair major tables: [0, 2048) float4 spectrum rows, [2048, 4096) W4096 rows,
-                              // [4096, 4224) W256 rows (runtime.cpp ols_build)
-    void* d_ostab = nullptr;  // one-shot kernel tables (kOlsOsTabF4 float4, runtime.cpp ols_build)
+                              // [4096, 4224) W256 rows (ols_tables.cpp ols_pack_pkt)
+    void* d_ostab = nullptr;  // one-shot kernel tables (kOlsOsTabF4 float4, ols_tables.cpp ols_os_bases)
                               // (C1 C2 | C3 D1 | D2 D3), then [16][8] float4 W256 rows
     // real taps (conjugate-symmetric spectrum): the half-spectrum table of the one-shot kernel,
-    // float4 [4][kOlsHalfRow] (runtime.cpp ols_build), else null
+    // float4 [4][kOlsHalfRow] (ols_tables.cpp ols_half_table), else null
     void* d_hhalf = nullptr;
     int sample_bytes = 8;  // 8: c32 samples; 4: real f32 samples and taps (kern_fir_ols_real.hip,
                            // which reads d_pkt and d_ostab only)
@@ -77,7 +77,7 @@ hipError_t launch_fir_ols_pk(const OlsPlan& p, const void* x, void* y, size_t n,
 constexpr int kOlsLongMinLog2N = 13, kOlsLongMaxLog2N = 22;
 constexpr size_t kOlsLongMaxLm1 = (size_t)1 << 20;
 struct OlsLongPlan {
-    const void* d_G = nullptr;    // [N1][N2] c32: G[k1 + N1 k2] * scale / N (runtime.cpp ols_long_build)
+    const void* d_G = nullptr;    // [N1][N2] c32: G[k1 + N1 k2] * scale / N (ols_tables.cpp ols_long_spectrum)
     const void* d_tw1 = nullptr;  // [N1] c32 e^{-j 2 pi m / N1}
     const void* d_tw2 = nullptr;  // [N2] c32 e^{-j 2 pi m / N2}
     int log2n = 0;

@@ -172,7 +172,7 @@ __device__ __forceinline__ void mirror_products(f2 a0, f2 a1, float4 m, f2& r0, 
 //          through DPP (mirror_products): four 16-byte spectrum loads per lane instead of eight.  The 16
 //          lanes of row 0, whose mirror (0, 16 - k1) is no DPP partner, load their mirror's four
 //          pairs as well (wave 3 only).  Same bits as the full-table form on a table with
-//          H[N - k] = conj H[k] exactly (runtime.cpp ols_build makes it so).  Otherwise Hs is
+//          H[N - k] = conj H[k] exactly (ols_tables.cpp ols_spectrum makes it so).  Otherwise Hs is
 //          the full table, float4 [8][256].
 // The form of this function decides the instruction schedule of its callers, their prologues'
 // load order included (kern_fir_ols_os.hip), so each of these is load-bearing; with them the c32

@@ -314,7 +314,7 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
     const auto rh = __builtin_amdgcn_make_buffer_rsrc((void*)Hs, (short)0,
                                                       (ABL & (268435456 | 1048576 | 8388608)) ? 4 * kOlsHalfRow * 16 : 2048 * 16, kBufWord3);
     constexpr int kLdAux = (ABL & 16384) ? 0 : 2;  // nontemporal (aux 2)
-    // twiddle bases: column t of W4096, row lo4 of W256 (runtime.cpp ols_build), requested
+    // twiddle bases: column t of W4096, row lo4 of W256 (ols_tables.cpp ols_os_bases), requested
     // before the segment's rows (L2 hits that land while the rows stream in)
     auto tab = [&](int lane, int off) {
         if constexpr ((ABL & 4096) != 0) {
@@ -496,7 +496,7 @@ __device__ __forceinline__ void ols_os_segment(const f2* __restrict__ xw, const 
         // H[N - k] = conj H[k]): pairs p < 4 from the half table at lane t, pairs p >= 4 as the
         // conjugates of pair 7 - p of the mirror lane (16 - k0, 15 - k1) (k0 = 0: (0, 16 - k1); lane
         // (0, 0): the table's tail entry), halves swapped -- a 16 KB table instead of 32 KB, read with
-        // the same eight loads (runtime.cpp ols_build)
+        // the same eight loads (ols_tables.cpp ols_pack_pkt)
         if constexpr (kRg != 0) {
             // the lane's own pairs p < 4; row 0 alone also its mirror's (0, 16 - k1), as below
 #pragma unroll
