@@ -463,6 +463,58 @@ SDSP_API int sdsp_nco_mix_block_device(sdsp_nco* h, int down, int precision, con
 SDSP_API int sdsp_nco_synchronize(sdsp_nco* h);
 
 /* ------------------------------------------------------------------------
+ * Digital down-converter: NCO mix-down fused into the decimating FIR.  A
+ * build-defined composition of two reference objects (as the channeliser is):
+ * a handle with taps, scale, decimation M and an oscillator (theta, delta_theta)
+ * is, sample for sample,
+ *     v = nco.mix_down(x[i]); nco.step(); decimator.push/execute(v)
+ * i.e. sdsp_nco_mix_block(down) followed by sdsp_fir_execute_block on a
+ * sdsp_decim_create handle, without the mixed stream's round trip through
+ * memory.  The delay line holds mixed samples (the last len - 1, oldest first,
+ * the decimator's layout); after a block of n samples theta += n * delta_theta
+ * (wrapping) and the decimator phase advances as sdsp_fir_* does.  Channels are
+ * channel-major and share the oscillator, the sample index counted within the
+ * channel.  dtype: the complex-sample pairs SDSP_RC32, SDSP_CC32, SDSP_RC64,
+ * SDSP_CC64; len >= 1 and decimation >= 1 as sdsp_decim_create (a real dtype,
+ * len = 0 or decimation = 0 fails with SDSP_E_INVALID_ARGUMENT).  Algorithms: SDSP_ALGO_EXACT (bit-identical to the
+ * two-handle composition on their EXACT paths), SDSP_ALGO_FMA, SDSP_ALGO_AUTO
+ * (FMA from 65536 32-bit inputs per call, as the decimator); SDSP_ALGO_FFT fails
+ * with SDSP_E_UNSUPPORTED.  New handles start on the process default
+ * (sdsp_set_default_algo).  Block entry points only: stream ordering, staging,
+ * the refusal of overlapping blocks and the error strings follow
+ * sdsp_fir_execute_block[_device].
+ * ------------------------------------------------------------------------ */
+typedef struct sdsp_ddc sdsp_ddc;
+SDSP_API int sdsp_ddc_create(sdsp_ddc** out, int dtype, const void* taps, size_t len, const void* scale,
+                             size_t decimation, int device);
+SDSP_API void sdsp_ddc_destroy(sdsp_ddc* h);
+/* same taps, knobs, delay line, decimator phase and oscillator state */
+SDSP_API int sdsp_ddc_clone(const sdsp_ddc* h, sdsp_ddc** out);
+/* zeroed delay line, decimator phase 0, theta = delta_theta = 0 (NCO::reset) */
+SDSP_API int sdsp_ddc_reset(sdsp_ddc* h);
+SDSP_API int sdsp_ddc_set_channels(sdsp_ddc* h, size_t channels); /* resets the delay lines */
+SDSP_API int sdsp_ddc_set_algo(sdsp_ddc* h, int algo);
+SDSP_API int sdsp_ddc_get_algo(const sdsp_ddc* h);
+SDSP_API int sdsp_ddc_set_direction(sdsp_ddc* h, int up); /* 0 = mix_down (default), 1 = mix_up */
+SDSP_API int sdsp_ddc_set_frequency(sdsp_ddc* h, double delta_theta);   /* NCO :59-61 */
+SDSP_API int sdsp_ddc_adjust_frequency(sdsp_ddc* h, double dt);         /* NCO :64-66 */
+SDSP_API int sdsp_ddc_set_phase(sdsp_ddc* h, double phi);               /* NCO :79-81 */
+SDSP_API int sdsp_ddc_adjust_phase(sdsp_ddc* h, double delta_phi);      /* NCO :84-86 */
+SDSP_API int sdsp_ddc_get_nco_state(const sdsp_ddc* h, uint32_t* theta, uint32_t* delta_theta);
+SDSP_API int sdsp_ddc_set_nco_state(sdsp_ddc* h, uint32_t theta, uint32_t delta_theta);
+SDSP_API size_t sdsp_ddc_output_count(const sdsp_ddc* h, size_t n);
+SDSP_API int sdsp_ddc_execute_block(sdsp_ddc* h, const void* in, size_t n, void* out, size_t* n_out);
+SDSP_API int sdsp_ddc_execute_block_device(sdsp_ddc* h, const void* d_in, size_t n, void* d_out, size_t* n_out,
+                                           void* stream);
+/* delay line ([channels][len-1] mixed samples, oldest first) and decimator phase, as sdsp_fir_* */
+SDSP_API size_t sdsp_ddc_state_len(const sdsp_ddc* h);
+SDSP_API int sdsp_ddc_get_state(const sdsp_ddc* h, void* hist, size_t* phase);
+SDSP_API int sdsp_ddc_set_state(sdsp_ddc* h, const void* hist, size_t phase);
+/* kernel-variant knob: SDSP_TUNE_DECIM_SEG (performance only) */
+SDSP_API int sdsp_ddc_set_tuning(sdsp_ddc* h, int key, int value);
+SDSP_API int sdsp_ddc_synchronize(sdsp_ddc* h);
+
+/* ------------------------------------------------------------------------
  * AGC (src/auto_gain_control/mod.rs:97-677), SURVEY §8f row 4.  A handle is a
  * bank of `channels` independent AGCs (channel-major sample buffers) with
  * device-resident state; one lane per channel runs the reference's per-sample

@@ -17,6 +17,8 @@ from .nco import NCO, NCOError  # noqa: F401
 from . import auto_gain_control  # noqa: F401
 from .auto_gain_control import AGC, AGCError, AGCErrorCode, SquelchMode  # noqa: F401
 from .filter.auto_correlator import AutoCorrelator  # noqa: F401
+from . import ddc  # noqa: F401
+from .ddc import DDC  # noqa: F401
 from .filter import (Filter, FIRFilter, DecimatingFIRFilter, PolyPhaseFilterBank,  # noqa: F401
                      InterpolatingFIRFilter, IIRFilter, IIRFilterType, SecondOrderFilter, DecimatingIIRFilter,
                      InterpolatingIIRFilter)

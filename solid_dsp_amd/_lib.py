@@ -130,6 +130,29 @@ def _declare(L):
         "sdsp_pfb_frequency_response": (i, [vp, d, dp]),
         "sdsp_pfb_group_delay": (i, [vp, d, dp]),
         "sdsp_pfb_synchronize": (i, [vp]),
+        # digital down-converter (NCO mix-down fused into the decimating FIR)
+        "sdsp_ddc_create": (i, [vpp, i, vp, sz, vp, sz, i]),
+        "sdsp_ddc_destroy": (None, [vp]),
+        "sdsp_ddc_clone": (i, [vp, vpp]),
+        "sdsp_ddc_reset": (i, [vp]),
+        "sdsp_ddc_set_channels": (i, [vp, sz]),
+        "sdsp_ddc_set_algo": (i, [vp, i]),
+        "sdsp_ddc_get_algo": (i, [vp]),
+        "sdsp_ddc_set_direction": (i, [vp, i]),
+        "sdsp_ddc_set_frequency": (i, [vp, d]),
+        "sdsp_ddc_adjust_frequency": (i, [vp, d]),
+        "sdsp_ddc_set_phase": (i, [vp, d]),
+        "sdsp_ddc_adjust_phase": (i, [vp, d]),
+        "sdsp_ddc_get_nco_state": (i, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "sdsp_ddc_set_nco_state": (i, [vp, C.c_uint32, C.c_uint32]),
+        "sdsp_ddc_output_count": (sz, [vp, sz]),
+        "sdsp_ddc_execute_block": (i, [vp, vp, sz, vp, szp]),
+        "sdsp_ddc_execute_block_device": (i, [vp, vp, sz, vp, szp, vp]),
+        "sdsp_ddc_state_len": (sz, [vp]),
+        "sdsp_ddc_get_state": (i, [vp, vp, szp]),
+        "sdsp_ddc_set_state": (i, [vp, vp, sz]),
+        "sdsp_ddc_set_tuning": (i, [vp, i, i]),
+        "sdsp_ddc_synchronize": (i, [vp]),
         "sdsp_synth_f32_device": (i, [vp, C.c_uint64, C.c_uint64, C.c_uint64, sz, vp]),
         "sdsp_bandwidth_copy_device": (i, [vp, vp, sz, vp]),
         "sdsp_firdes_kaiser": (i, [sz, d, d, d, dp]),

@@ -18,151 +18,16 @@
 //
 // Summation order differs from the reference (phase-major partials, fused
 // multiply-add), so this is the FMA path; SDSP_ALGO_EXACT keeps the
-// reference-order kernel in kern_fir_direct.hip.
+// reference-order kernel in kern_fir_direct.hip.  The walk itself (poly_group) lives in
+// sdsp_decim_walk.hpp, which the down-converter shares; this unit instantiates it with the
+// identity load hook.
+#include "sdsp_decim_walk.hpp"
 #include "sdsp_device.hpp"
 #include "sdsp_kernels.hpp"
 
 namespace sdsp {
 
 namespace {
-
-constexpr int kPolyThreads = 256;
-constexpr int kPolyWaves = kPolyThreads / 64;
-
-template <typename I>
-__device__ __forceinline__ I ext_at(const I* __restrict__ x, const I* __restrict__ hist, long long j, long long n,
-                                    int Lm1) {
-    if (j >= 0) return j < n ? x[j] : zero_v<I>();
-    const long long h = (long long)Lm1 + j;
-    return h >= 0 ? hist[h] : zero_v<I>();
-}
-
-__device__ __forceinline__ float shfl_xor_v(float v, int d) { return __shfl_xor(v, d); }
-__device__ __forceinline__ double shfl_xor_v(double v, int d) { return __shfl_xor(v, d); }
-template <typename T> __device__ __forceinline__ cpx<T> shfl_xor_v(cpx<T> v, int d) {
-    return {__shfl_xor(v.re, d), __shfl_xor(v.im, d)};
-}
-
-// streaming (non-temporal) load of a 4/8/16-byte value: the input is read once
-template <typename T> __device__ __forceinline__ T nt_load(const T* p) {
-    typedef unsigned u1v __attribute__((ext_vector_type(1)));
-    typedef unsigned u2v __attribute__((ext_vector_type(2)));
-    typedef unsigned u4v __attribute__((ext_vector_type(4)));
-    T out;
-    if constexpr (sizeof(T) == 16) {
-        const u4v v = __builtin_nontemporal_load(reinterpret_cast<const u4v*>(p));
-        __builtin_memcpy(&out, &v, 16);
-    } else if constexpr (sizeof(T) == 8) {
-        const u2v v = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(p));
-        __builtin_memcpy(&out, &v, 8);
-    } else {
-        static_assert(sizeof(T) == 4, "nt_load size");
-        const u1v v = __builtin_nontemporal_load(reinterpret_cast<const u1v*>(p));
-        __builtin_memcpy(&out, &v, 4);
-    }
-    return out;
-}
-
-// V adjacent columns per lane: one 16-byte load per lane and row when the row
-// start is 16-byte aligned (V = 16 / sizeof(I)), else one sample per lane.
-template <typename I, int V> struct alignas(V * sizeof(I)) IVec {
-    I e[V];
-};
-
-template <typename I, int M, int K, int V> struct PolyGeom {
-    static constexpr int MV = M / V;                      // lanes per group
-    static constexpr int G = 64 / MV;                     // groups per wave
-    static constexpr int CH = K > MV / 4 ? K : MV / 4;    // rows per reduction chunk
-    static constexpr int P = MV > CH ? MV / CH : 1;       // lanes per output in the reduction (<= 4)
-    static constexpr int RPL = CH > MV ? CH / MV : 1;     // outputs per lane when CH >= MV
-    // one 8-byte slot of padding per row: lane (r, part) of the reduction reads
-    // slot r*(MV*sizeof(I)/8 + 1) + part*CH*sizeof(I)/8, distinct mod 32 within a group
-    static constexpr int RB = MV * (int)sizeof(I) + 8;
-    static constexpr int LDS_WAVE = G * CH * RB;
-};
-
-template <typename C, typename I, int M, int K, int V, bool INTERIOR>
-__device__ __forceinline__ void poly_group(const I* __restrict__ x, const I* __restrict__ hist,
-                                           const C (&tap)[K][V], C scale, I* __restrict__ y,
-                                           char* __restrict__ tile, long long n, int Lm1, long long j0,
-                                           long long m_begin, long long m_end, int q) {
-    using Geo = PolyGeom<I, M, K, V>;
-    constexpr int CH = Geo::CH, MV = Geo::MV, RB = Geo::RB;
-    constexpr int SPC = CH / K;  // K-row steps per chunk
-    const long long nchunks = (m_end - m_begin + CH - 1) / CH;
-    const long long nsteps = 1 + nchunks * SPC;
-    const long long rho0 = m_begin - K;
-    // sample index of X[rho][q*V] = jq + rho*M
-    const long long jq = j0 - (M - 1) + q * V;
-
-    using Vec = IVec<I, V>;
-    I acc[K];
-    Vec cur[K], nxt[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = zero_v<I>();
-
-    auto load = [&](Vec (&v)[K], long long rho) {
-#pragma unroll
-        for (int u = 0; u < K; ++u) {
-            const long long j = jq + (rho + u) * M;
-            if constexpr (INTERIOR) {
-                v[u] = nt_load(reinterpret_cast<const Vec*>(x + j));
-            } else {
-#pragma unroll
-                for (int e = 0; e < V; ++e) v[u].e[e] = ext_at(x, hist, j + e, n, Lm1);
-            }
-        }
-    };
-
-    load(cur, rho0);
-    for (long long s = 0; s < nsteps; ++s) {
-        if (s + 1 < nsteps) load(nxt, rho0 + (s + 1) * K);
-        const int trow = (int)((s - 1) % SPC) * K;  // tile row of this step's first row (s >= 1)
-#pragma unroll
-        for (int u = 0; u < K; ++u) {
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-#pragma unroll
-                for (int e = 0; e < V; ++e) acc[(u + k) % K] = fmac_(acc[(u + k) % K], tap[k][e], cur[u].e[e]);
-            if (s > 0) *reinterpret_cast<I*>(tile + (trow + u) * RB + q * (int)sizeof(I)) = acc[u];
-            acc[u] = zero_v<I>();
-        }
-        if (s > 0 && s % SPC == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const long long c = m_begin + (s / SPC - 1) * CH;
-            if constexpr (CH >= MV) {
-                // lane q sums whole rows q, q + MV, ...
-#pragma unroll
-                for (int t = 0; t < Geo::RPL; ++t) {
-                    const int r = q + t * MV;
-                    const I* row = reinterpret_cast<const I*>(tile + r * RB);
-                    I sum = row[0];
-#pragma unroll
-                    for (int e = 1; e < MV; ++e) sum = add_(sum, row[e]);
-                    if (c + r < m_end) y[c + r] = mul_(sum, scale);
-                }
-            } else {
-                // output r = q % CH: lane part q / CH sums columns [part*CH, part*CH+CH),
-                // then the P parts combine across lanes q ^ CH, q ^ 2CH
-                const int r = q % CH, part = q / CH;
-                const I* row = reinterpret_cast<const I*>(tile + r * RB) + part * CH;
-                I sum = row[0];
-#pragma unroll
-                for (int e = 1; e < CH; ++e) sum = add_(sum, row[e]);
-#pragma unroll
-                for (int d = CH; d < MV; d *= 2) sum = add_(sum, shfl_xor_v(sum, d));
-                if (part == 0 && c + r < m_end) y[c + r] = mul_(sum, scale);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-#pragma unroll
-        for (int u = 0; u < K; ++u) cur[u] = nxt[u];
-    }
-}
 
 template <typename C, typename I, int M, int K, int V>
 __global__ void __launch_bounds__(kPolyThreads)
@@ -198,21 +63,18 @@ decim_poly_kernel(const I* __restrict__ x, const I* __restrict__ hist, const C* 
     const long long last_row = (wave_id * G + G - 1) * seg + (seg + CH - 1) / CH * CH - 1;
     const long long last_j = j0 + last_row * M;
     if (first_j >= 0 && last_j < n)
-        poly_group<C, I, M, K, V, true>(x, hist, tap, scale, y, tile, n, L - 1, j0, m_begin, m_end, q);
+        poly_group<C, I, M, K, V, true>(x, hist, tap, scale, y, tile, n, L - 1, j0, m_begin, m_end, q,
+                                        LoadIdentity{});
     else
-        poly_group<C, I, M, K, V, false>(x, hist, tap, scale, y, tile, n, L - 1, j0, m_begin, m_end, q);
+        poly_group<C, I, M, K, V, false>(x, hist, tap, scale, y, tile, n, L - 1, j0, m_begin, m_end, q,
+                                        LoadIdentity{});
 }
 
 template <typename C, typename I, int M, int K, int V>
 hipError_t launch_poly_t(const FirArgs& a, hipStream_t s) {
     using Geo = PolyGeom<I, M, K, V>;
     const long long nout = (long long)a.nout;
-    // outputs per group: a multiple of CH.  64-256 measured fastest on cfg4; 256 keeps the
-    // K warm-up rows per group (re-read input) to ~3% of the traffic
-    long long seg = a.seg > 0 ? a.seg : (nout + 8191) / 8192;
-    if (a.seg <= 0 && seg > 256) seg = 256;
-    seg = (seg + Geo::CH - 1) / Geo::CH * Geo::CH;
-    if (seg < Geo::CH) seg = Geo::CH;
+    const long long seg = poly_seg(a.seg, nout, Geo::CH);  // outputs per group: a multiple of CH
     const long long groups = (nout + seg - 1) / seg;
     const long long waves = (groups + Geo::G - 1) / Geo::G;
     dim3 grid((unsigned)((waves + kPolyWaves - 1) / kPolyWaves), (unsigned)a.channels);

@@ -36,6 +36,7 @@
 #include <tuple>
 #include "sdsp_device.hpp"
 #include "sdsp_kernels.hpp"
+#include "sdsp_nco_dev.hpp"
 
 namespace sdsp {
 
@@ -48,8 +49,6 @@ constexpr int kChunk = 256;          // j-terms staged per pass
 // one spare slot per 8: lane t reads slot 8t + o, i.e. LDS element 9t + ..., so the
 // 32 (c32) or 16 (c64) lanes of one LDS cycle hit distinct banks
 __host__ __device__ constexpr int pad8(int s) { return s + (s >> 3); }
-
-template <typename T> __device__ inline cpx<T> conj_(cpx<T> a) { return {a.re, -a.im}; }
 
 // a * conj(c) with num-complex rounding (mul_(a, conj_(c)): re = a.re c.re - a.im (-c.im), im =
 // a.re (-c.im) + a.im c.re, every product rounded, no fma) in three packed instructions for c32:
@@ -400,15 +399,6 @@ __global__ void __launch_bounds__(256) acorr_energy_kernel(const cpx<T>* __restr
         __syncthreads();
     }
     if (threadIdx.x == 0) energy[ch] = part[0];
-}
-
-template <typename T, bool DOWN>
-__device__ __forceinline__ cpx<T> nco_one(const T* lut, cpx<T> v, long long i, uint32_t theta0, uint32_t dtheta) {
-    const uint32_t th = theta0 + (uint32_t)i * dtheta;  // wrapping u32: theta_0 + i dtheta mod 2^32
-    const uint32_t idx = ((th + (1u << 21)) >> 22) & 0x3ffu;
-    cpx<T> ph = {lut[(idx + 256) & 0x3ffu], lut[idx]};
-    if constexpr (DOWN) ph = conj_(ph);
-    return mul_(ph, v);
 }
 
 // One-shot, XCD-ordered: a workgroup mixes kU x 256 consecutive V-sample vectors

@@ -21,15 +21,22 @@ namespace {
 size_t cbytes(int prec) { return prec == 0 ? 8 : 16; }
 int hist_dtype(int prec) { return prec == 0 ? SDSP_RC32 : SDSP_RC64; }  // sample size 8 / 16 bytes
 
-// constrain()  src/nco/mod.rs:175-187
-uint32_t constrain(double theta) {
+}  // namespace
+
+namespace sdsp {
+// nco_constrain()  src/nco/mod.rs:175-187 (the NCO and the down-converter share this copy)
+uint32_t nco_constrain(double theta) {
     const double d = theta / (2.0 * M_PI);
     double f = d - std::trunc(d);  // f64::fract
     if (f < 0.0) f += 1.0;
     return (uint32_t)(f * (double)0xffffffffu);
 }
+// NCO::new's sine table  src/nco/mod.rs:36-50
+void nco_sine_table(double* table) {
+    for (int i = 0; i < 1024; ++i) table[i] = std::sin(2.0 * M_PI * (double)i / 1024.0);
+}
+}  // namespace sdsp
 
-}  // namespace
 
 // ===========================================================================
 // AutoCorrelator
@@ -218,7 +225,7 @@ int sdsp_nco_create(sdsp_nco** out, int device) {  // NCO::new  src/nco/mod.rs:3
     DeviceGuard g(device);
     auto* h = new sdsp_nco();
     h->cus = cus;
-    for (int i = 0; i < 1024; ++i) h->table[i] = std::sin(2.0 * M_PI * (double)i / 1024.0);
+    nco_sine_table(h->table);
     h->alpha = 0.1;
     h->beta = std::sqrt(h->alpha);
     if (h->open(device) != hipSuccess) {
@@ -244,15 +251,15 @@ int sdsp_nco_reset(sdsp_nco* h) {  // :53-56
     h->delta_theta = 0;
     return SDSP_OK;
 }
-uint32_t sdsp_nco_constrain(double theta) { return constrain(theta); }  // :175-187
+uint32_t sdsp_nco_constrain(double theta) { return nco_constrain(theta); }  // :175-187
 int sdsp_nco_set_frequency(sdsp_nco* h, double dtheta) {  // :59-61
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->delta_theta = constrain(dtheta);
+    h->delta_theta = nco_constrain(dtheta);
     return SDSP_OK;
 }
 int sdsp_nco_adjust_frequency(sdsp_nco* h, double dt) {  // :64-66 (u32 add wraps in release builds)
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->delta_theta += constrain(dt);
+    h->delta_theta += nco_constrain(dt);
     return SDSP_OK;
 }
 // get_frequency (:69-76): (delta_theta as u64 / 2^32) is integer division, always 0 for a u32
@@ -263,12 +270,12 @@ double sdsp_nco_get_frequency(const sdsp_nco* h) {
 }
 int sdsp_nco_set_phase(sdsp_nco* h, double phi) {  // :79-81
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->theta = constrain(phi);
+    h->theta = nco_constrain(phi);
     return SDSP_OK;
 }
 int sdsp_nco_adjust_phase(sdsp_nco* h, double dphi) {  // :84-86
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->theta += constrain(dphi);
+    h->theta += nco_constrain(dphi);
     return SDSP_OK;
 }
 double sdsp_nco_get_phase(const sdsp_nco* h) {  // :89-91 (integer division as get_frequency)
@@ -297,8 +304,8 @@ int sdsp_nco_set_internal_pll_bandwidth(sdsp_nco* h, double bandwidth) {  // :12
 }
 int sdsp_nco_pll_step(sdsp_nco* h, double delta_phi) {  // :135-138
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->delta_theta += constrain(delta_phi * h->alpha);
-    h->theta += constrain(delta_phi * h->beta);
+    h->delta_theta += nco_constrain(delta_phi * h->alpha);
+    h->theta += nco_constrain(delta_phi * h->beta);
     return SDSP_OK;
 }
 int sdsp_nco_get_state(const sdsp_nco* h, uint32_t* theta, uint32_t* delta_theta) {

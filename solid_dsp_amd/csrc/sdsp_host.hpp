@@ -36,6 +36,11 @@ int device_status(hipError_t e, const char* what);
         if (_e != hipSuccess) return device_status(_e, what); \
     } while (0)
 
+// the NCO's phase arithmetic (runtime_rx.cpp): constrain() of an angle to the u32 phase register,
+// and the 1024-entry f64 sine table of NCO::new
+uint32_t nco_constrain(double theta);
+void nco_sine_table(double* table);
+
 // SDSP_OK when `device` is a usable gfx950 device, SDSP_E_NO_DEVICE otherwise; *cus (when given)
 // receives its compute-unit count
 int check_device(int device, int* cus);

@@ -222,6 +222,18 @@ hipError_t launch_acorr_energy(int prec, const void* x, const void* hist, size_t
 // NCO mix_up / mix_down over a block (kern_rx.hip): theta_i = theta0 + i dtheta (u32)
 hipError_t launch_nco_mix(int prec, bool down, const void* x, void* y, size_t n, const double* table, uint32_t theta0,
                           uint32_t dtheta, int num_cus, hipStream_t s);
+// Digital down-converter (kern_ddc.hip): the decimator of `fir` (complex-sample dtypes; exact = the
+// reference-order walk, else the polyphase walk where its shape rule admits L and M) with every
+// sample of the call multiplied by the oscillator's phasor at theta0 + i dtheta on the load path;
+// fir.hist holds mixed samples.  launch_ddc_hist writes the next history to new_hist.
+struct DdcArgs {
+    FirArgs fir;
+    const double* table;  // device copy of the 1024-entry f64 sine table
+    uint32_t theta0, dtheta;
+    bool down;
+};
+hipError_t launch_ddc(int dtype, const DdcArgs& d, hipStream_t s);
+hipError_t launch_ddc_hist(int dtype, const DdcArgs& d, void* new_hist, hipStream_t s);
 // AGC bank (src/auto_gain_control/mod.rs): state is sdsp_agc_state[channels] in
 // device memory; cplx = Complex<f64> samples, else f64
 // pipe: agc_pipe_kernel for calls it admits (SDSP_TUNE_AGC_KERNEL 0), else agc_kernel
