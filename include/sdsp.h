@@ -515,6 +515,65 @@ SDSP_API int sdsp_ddc_set_tuning(sdsp_ddc* h, int key, int value);
 SDSP_API int sdsp_ddc_synchronize(sdsp_ddc* h);
 
 /* ------------------------------------------------------------------------
+ * Digital up-converter: NCO mix-up fused into the interpolating FIR.  A
+ * build-defined composition of two reference objects (as the down-converter
+ * and the channeliser are): a handle with taps, interpolation M and an
+ * oscillator (theta, delta_theta) is, sample for sample,
+ *     y = interpolator.execute(x[j])                  (M outputs, interp.rs:93-111)
+ *     for p in 0..M: out[j*M + p] = nco.mix_up(y[p]); nco.step()
+ * i.e. sdsp_pfb_execute_block on a sdsp_interp_create handle followed by
+ * sdsp_nco_mix_block(down = 0), without the interpolated stream's round trip
+ * through memory.
+ *   dtype: the complex-sample pairs SDSP_RC32, SDSP_CC32, SDSP_RC64, SDSP_CC64;
+ *     a real dtype or one out of range fails with SDSP_E_INVALID_ARGUMENT.
+ *   len = 0 and interpolation = 0 fail with the interpolator's own codes,
+ *     SDSP_E_COEFFICIENTS_LENGTH_ZERO and SDSP_E_INTERPOLATION_LESS_THAN_ONE,
+ *     before the device is looked at.
+ *   Sub-filter length K (computed in f32), zero padding of the taps and the
+ *     branch layout are sdsp_interp_create's.  There is no scale: the
+ *     interpolator has none.
+ *   Oscillator: theta and delta_theta are u32 host registers read at launch, as
+ *     in sdsp_ddc.  Output o = j*M + p of a channel is mixed with the phasor at
+ *     theta + (u32)o * delta_theta; after a block of n inputs
+ *     theta += (u32)(n*M) * delta_theta, wrapping.  Channels are channel-major
+ *     and share the oscillator, the output index counted within the channel.
+ *   Direction: mix_up by default; sdsp_duc_set_direction(h, 1) selects mix_down.
+ *   Precision: 32-bit pairs use the f32 sine table and product, 64-bit pairs
+ *     the f64 ones (sdsp_nco_mix_block's precision 0 / 1).
+ *   Window: the last K unmixed inputs per channel, oldest first.
+ *   Algorithms: SDSP_ALGO_EXACT (bit-identical to the two-handle composition on
+ *     its EXACT path) and SDSP_ALGO_FMA; anything else fails with
+ *     SDSP_E_INVALID_ARGUMENT, as sdsp_pfb_set_algo.  New handles follow the
+ *     process default as interpolators do: FMA when it is FMA, else EXACT.
+ *   Block entry points only: stream ordering, host staging, the refusal of
+ *     overlapping blocks, n = 0 and the error strings follow
+ *     sdsp_pfb_execute_block[_device].  The output holds n * M samples per channel.
+ * ------------------------------------------------------------------------ */
+typedef struct sdsp_duc sdsp_duc;
+SDSP_API int sdsp_duc_create(sdsp_duc** out, int dtype, const void* taps, size_t len, size_t interpolation,
+                             int device);
+SDSP_API void sdsp_duc_destroy(sdsp_duc* h);
+/* same taps, algorithm, direction, window and oscillator state */
+SDSP_API int sdsp_duc_clone(const sdsp_duc* h, sdsp_duc** out);
+/* zeroed window, theta = delta_theta = 0 (NCO::reset) */
+SDSP_API int sdsp_duc_reset(sdsp_duc* h);
+SDSP_API int sdsp_duc_set_channels(sdsp_duc* h, size_t channels); /* resets the windows */
+SDSP_API int sdsp_duc_set_algo(sdsp_duc* h, int algo);
+SDSP_API int sdsp_duc_get_algo(const sdsp_duc* h);
+SDSP_API int sdsp_duc_set_direction(sdsp_duc* h, int down); /* 0 = mix_up (default), 1 = mix_down */
+SDSP_API int sdsp_duc_set_frequency(sdsp_duc* h, double delta_theta);   /* NCO :59-61 */
+SDSP_API int sdsp_duc_adjust_frequency(sdsp_duc* h, double dt);         /* NCO :64-66 */
+SDSP_API int sdsp_duc_set_phase(sdsp_duc* h, double phi);               /* NCO :79-81 */
+SDSP_API int sdsp_duc_adjust_phase(sdsp_duc* h, double delta_phi);      /* NCO :84-86 */
+SDSP_API int sdsp_duc_get_nco_state(const sdsp_duc* h, uint32_t* theta, uint32_t* delta_theta);
+SDSP_API int sdsp_duc_set_nco_state(sdsp_duc* h, uint32_t theta, uint32_t delta_theta);
+SDSP_API size_t sdsp_duc_interpolation(const sdsp_duc* h);
+SDSP_API size_t sdsp_duc_subfilter_len(const sdsp_duc* h);
+SDSP_API int sdsp_duc_execute_block(sdsp_duc* h, const void* in, size_t n, void* out);
+SDSP_API int sdsp_duc_execute_block_device(sdsp_duc* h, const void* d_in, size_t n, void* d_out, void* stream);
+SDSP_API int sdsp_duc_synchronize(sdsp_duc* h);
+
+/* ------------------------------------------------------------------------
  * AGC (src/auto_gain_control/mod.rs:97-677), SURVEY §8f row 4.  A handle is a
  * bank of `channels` independent AGCs (channel-major sample buffers) with
  * device-resident state; one lane per channel runs the reference's per-sample

@@ -19,6 +19,8 @@ from .auto_gain_control import AGC, AGCError, AGCErrorCode, SquelchMode  # noqa:
 from .filter.auto_correlator import AutoCorrelator  # noqa: F401
 from . import ddc  # noqa: F401
 from .ddc import DDC  # noqa: F401
+from . import duc  # noqa: F401
+from .duc import DUC  # noqa: F401
 from .filter import (Filter, FIRFilter, DecimatingFIRFilter, PolyPhaseFilterBank,  # noqa: F401
                      InterpolatingFIRFilter, IIRFilter, IIRFilterType, SecondOrderFilter, DecimatingIIRFilter,
                      InterpolatingIIRFilter)

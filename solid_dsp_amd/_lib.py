@@ -153,6 +153,25 @@ def _declare(L):
         "sdsp_ddc_set_state": (i, [vp, vp, sz]),
         "sdsp_ddc_set_tuning": (i, [vp, i, i]),
         "sdsp_ddc_synchronize": (i, [vp]),
+        "sdsp_duc_create": (i, [vpp, i, vp, sz, sz, i]),
+        "sdsp_duc_destroy": (None, [vp]),
+        "sdsp_duc_clone": (i, [vp, vpp]),
+        "sdsp_duc_reset": (i, [vp]),
+        "sdsp_duc_set_channels": (i, [vp, sz]),
+        "sdsp_duc_set_algo": (i, [vp, i]),
+        "sdsp_duc_get_algo": (i, [vp]),
+        "sdsp_duc_set_direction": (i, [vp, i]),
+        "sdsp_duc_set_frequency": (i, [vp, d]),
+        "sdsp_duc_adjust_frequency": (i, [vp, d]),
+        "sdsp_duc_set_phase": (i, [vp, d]),
+        "sdsp_duc_adjust_phase": (i, [vp, d]),
+        "sdsp_duc_get_nco_state": (i, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "sdsp_duc_set_nco_state": (i, [vp, C.c_uint32, C.c_uint32]),
+        "sdsp_duc_interpolation": (sz, [vp]),
+        "sdsp_duc_subfilter_len": (sz, [vp]),
+        "sdsp_duc_execute_block": (i, [vp, vp, sz, vp]),
+        "sdsp_duc_execute_block_device": (i, [vp, vp, sz, vp, vp]),
+        "sdsp_duc_synchronize": (i, [vp]),
         "sdsp_synth_f32_device": (i, [vp, C.c_uint64, C.c_uint64, C.c_uint64, sz, vp]),
         "sdsp_bandwidth_copy_device": (i, [vp, vp, sz, vp]),
         "sdsp_firdes_kaiser": (i, [sz, d, d, d, dp]),

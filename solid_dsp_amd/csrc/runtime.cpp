@@ -844,17 +844,7 @@ int sdsp_fir_synchronize(sdsp_fir* h) {
 // ===========================================================================
 // Polyphase filterbank / interpolating FIR
 // ===========================================================================
-struct sdsp_pfb : HandleCore {
-    int dtype = 0;
-    size_t M = 0, K = 0, channels = 1;
-    bool interp = false;
-    std::vector<unsigned char> cb;     // [M][K] branch coefficients, stored order
-    std::vector<unsigned char> scale;  // kept, never applied (pfb.rs:85-90)
-    DevBuf d_cb;
-    PingPong hist;  // [channels][K] : the Window(K), oldest first
-    int algo = SDSP_ALGO_EXACT;
-};
-
+// (struct sdsp_pfb: sdsp_host.hpp, shared with the up-converter's runtime_duc.cpp)
 namespace {
 
 int pfb_alloc_state(sdsp_pfb* h) {

@@ -285,6 +285,24 @@ template <typename H> void destroy_handle(H* h) {
     delete h;
 }
 
+}  // namespace sdsp
+
+// Polyphase filterbank / interpolating FIR handle (runtime.cpp).  Defined here because the
+// up-converter (runtime_duc.cpp) is an interpolator handle plus an oscillator and launches its own
+// kernels on the interpolator's coefficients and window.
+struct sdsp_pfb : sdsp::HandleCore {
+    int dtype = 0;
+    size_t M = 0, K = 0, channels = 1;
+    bool interp = false;
+    std::vector<unsigned char> cb;     // [M][K] branch coefficients, stored order
+    std::vector<unsigned char> scale;  // kept, never applied (pfb.rs:85-90)
+    sdsp::DevBuf d_cb;
+    sdsp::PingPong hist;  // [channels][K] : the Window(K), oldest first
+    int algo = SDSP_ALGO_EXACT;
+};
+
+namespace sdsp {
+
 // [a, a + na) and [b, b + nb) overlap (byte ranges)
 inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     if (!na || !nb) return false;

@@ -234,6 +234,16 @@ struct DdcArgs {
 };
 hipError_t launch_ddc(int dtype, const DdcArgs& d, hipStream_t s);
 hipError_t launch_ddc_hist(int dtype, const DdcArgs& d, void* new_hist, hipStream_t s);
+// Digital up-converter (kern_duc.hip): the interpolator of `pfb` (complex-sample dtypes, the kernels
+// and selection rule of launch_pfb) with every output o of a channel multiplied by the oscillator's
+// phasor at theta0 + o dtheta on the store path; pfb.hist holds unmixed inputs.
+struct DucArgs {
+    PfbArgs pfb;
+    const double* table;  // device copy of the 1024-entry f64 sine table
+    uint32_t theta0, dtheta;
+    bool down;
+};
+hipError_t launch_duc(int dtype, const DucArgs& d, hipStream_t s);
 // AGC bank (src/auto_gain_control/mod.rs): state is sdsp_agc_state[channels] in
 // device memory; cplx = Complex<f64> samples, else f64
 // pipe: agc_pipe_kernel for calls it admits (SDSP_TUNE_AGC_KERNEL 0), else agc_kernel
