@@ -193,8 +193,11 @@ typedef enum {
     SDSP_TUNE_OLS_LONG_LOG2N = 22, /* overlap-save with more than 3841 taps: log2 of the segment transform
                                       size N, 13..22 with N >= 2 (len - 1); 0 (default) = the smallest
                                       power of two >= 4 (len - 1) and >= 2^14.  Other handles accept 0 only */
-    SDSP_TUNE_OLS_LONG_SEGS = 23   /* the same path: segments per round of its three passes, 1..4096;
+    SDSP_TUNE_OLS_LONG_SEGS = 23,  /* the same path: segments per round of its three passes, 1..4096;
                                       0 (default) = what 256 MiB of scratch hold */
+    SDSP_TUNE_RESAMP_KERNEL = 24   /* rational resampler: 0 (default) automatic, 1 staged kernel, 2 one lane
+                                      per output, 3 branch-stationary lanes; a value whose kernel does not
+                                      apply to the handle's shape runs the automatic choice (sdsp_resamp_info) */
 } sdsp_tune_key;
 SDSP_API int sdsp_fir_set_tuning(sdsp_fir* h, int key, int value);
 SDSP_API void sdsp_fir_destroy(sdsp_fir* h);        /* Drop */
@@ -572,6 +575,74 @@ SDSP_API size_t sdsp_duc_subfilter_len(const sdsp_duc* h);
 SDSP_API int sdsp_duc_execute_block(sdsp_duc* h, const void* in, size_t n, void* out);
 SDSP_API int sdsp_duc_execute_block_device(sdsp_duc* h, const void* d_in, size_t n, void* d_out, void* stream);
 SDSP_API int sdsp_duc_synchronize(sdsp_duc* h);
+
+/* ------------------------------------------------------------------------
+ * Rational resampler: an M/D polyphase FIR that computes only the outputs it
+ * keeps.  A build-defined composition of reference objects (as the channeliser
+ * and the two converters are): a handle has taps, interpolation M >= 1,
+ * decimation D >= 1, a window of the last K inputs per channel and a phase
+ * counter c in [0, D), the number of interpolated samples since the last one
+ * kept (0 after create and reset).  With z what sdsp_pfb_execute_block on a
+ * sdsp_interp_create handle with the same taps, M and window writes for a call
+ * of n inputs per channel (n * M samples), a call writes
+ *     out[k] = z[u_k],  u_k = (k + 1) * D - 1 - c,  k = 0 .. n_out - 1
+ *     n_out  = floor((c + n * M) / D),  then  c <- (c + n * M) mod D
+ * which is the reference decimator's convention (it emits on counts D - 1,
+ * 2D - 1, ...; decim.rs) applied to the interpolated stream.  With
+ * j = u_k / M and p = u_k mod M,
+ *     out[k] = sum_{i<K} cb[p][i] * x[j - i]
+ * summed in that order from a zero accumulator, x[j - i] taken from the window
+ * for j - i < 0: the interpolator's own expression, for 1 / D of its outputs.
+ *   dtype: any of the six pairs.  Check order of create: dtype out of range and
+ *     null taps with len > 0 (SDSP_E_INVALID_ARGUMENT), decimation = 0
+ *     (SDSP_E_DECIMATION_LESS_THAN_ONE), decimation > 2^31 - 1
+ *     (SDSP_E_INVALID_ARGUMENT), then the interpolator's own checks
+ *     (SDSP_E_COEFFICIENTS_LENGTH_ZERO, SDSP_E_INTERPOLATION_LESS_THAN_ONE, the
+ *     device).  *out is null after every failure.
+ *   Sub-filter length K (computed in f32), zero padding of the taps and the
+ *     branch layout are sdsp_interp_create's.  There is no scale.
+ *   Channels are channel-major and share c: input [channels][n], output
+ *     [channels][n_out].
+ *   Algorithms: SDSP_ALGO_EXACT (bit-identical to the EXACT interpolator's
+ *     output taken at [D - 1 - c :: D]) and SDSP_ALGO_FMA; anything else fails
+ *     with SDSP_E_INVALID_ARGUMENT, as sdsp_pfb_set_algo.  New handles follow
+ *     the process default as interpolators do.
+ *   Block entry points only: stream ordering, host staging, the refusal of
+ *     overlapping blocks and the error strings follow
+ *     sdsp_pfb_execute_block[_device].  A call that emits nothing (n_out = 0)
+ *     still updates the window and advances c.
+ * ------------------------------------------------------------------------ */
+typedef struct sdsp_resamp sdsp_resamp;
+SDSP_API int sdsp_resamp_create(sdsp_resamp** out, int dtype, const void* taps, size_t len, size_t interpolation,
+                                size_t decimation, int device);
+SDSP_API void sdsp_resamp_destroy(sdsp_resamp* h);
+/* same taps, algorithm, kernel knob, window and phase */
+SDSP_API int sdsp_resamp_clone(const sdsp_resamp* h, sdsp_resamp** out);
+/* zeroed window, phase 0 */
+SDSP_API int sdsp_resamp_reset(sdsp_resamp* h);
+SDSP_API int sdsp_resamp_set_channels(sdsp_resamp* h, size_t channels); /* resets the windows and the phase */
+SDSP_API int sdsp_resamp_set_algo(sdsp_resamp* h, int algo);
+SDSP_API int sdsp_resamp_get_algo(const sdsp_resamp* h);
+/* kernel-variant knob: SDSP_TUNE_RESAMP_KERNEL (performance only) */
+SDSP_API int sdsp_resamp_set_tuning(sdsp_resamp* h, int key, int value);
+SDSP_API size_t sdsp_resamp_interpolation(const sdsp_resamp* h);
+SDSP_API size_t sdsp_resamp_decimation(const sdsp_resamp* h);
+SDSP_API size_t sdsp_resamp_subfilter_len(const sdsp_resamp* h);
+SDSP_API int sdsp_resamp_get_phase(const sdsp_resamp* h, size_t* phase);
+SDSP_API int sdsp_resamp_set_phase(sdsp_resamp* h, size_t phase); /* phase >= D: SDSP_E_INVALID_ARGUMENT */
+/* outputs per channel a block of n inputs produces from the handle's current phase */
+SDSP_API size_t sdsp_resamp_output_count(const sdsp_resamp* h, size_t n);
+SDSP_API int sdsp_resamp_execute_block(sdsp_resamp* h, const void* in, size_t n, void* out, size_t* n_out);
+SDSP_API int sdsp_resamp_execute_block_device(sdsp_resamp* h, const void* d_in, size_t n, void* d_out,
+                                              size_t* n_out, void* stream);
+/* the kernel the next call runs (1 staged, 2 per output, 3 branch-stationary) and its outputs per workgroup */
+SDSP_API int sdsp_resamp_info(const sdsp_resamp* h, int* kernel, size_t* tile);
+SDSP_API int sdsp_resamp_synchronize(sdsp_resamp* h);
+/* The two formulas above in 64-bit arithmetic; needs no handle and no device.
+ * SDSP_E_INVALID_ARGUMENT when interpolation or decimation is 0, phase >= decimation, or
+ * phase + n * interpolation does not fit 63 bits. */
+SDSP_API int sdsp_resamp_count(size_t interpolation, size_t decimation, size_t phase, size_t n, size_t* n_out,
+                               size_t* next_phase);
 
 /* ------------------------------------------------------------------------
  * AGC (src/auto_gain_control/mod.rs:97-677), SURVEY §8f row 4.  A handle is a

@@ -25,6 +25,7 @@ TUNE_OLS_KERNEL, TUNE_CHAN_XCD_ORDER = 14, 15
 TUNE_HOST_STEP, TUNE_HOST_BLOCK_MACS = 16, 17
 TUNE_FFT_GROUP, TUNE_FFT_WAVE1024, TUNE_ACORR_KERNEL, TUNE_AGC_KERNEL = 18, 19, 20, 21
 TUNE_OLS_LONG_LOG2N, TUNE_OLS_LONG_SEGS = 22, 23
+TUNE_RESAMP_KERNEL = 24
 
 _PAIRS = {
     (np.dtype(np.float32), np.dtype(np.float32)): RR32,
@@ -172,6 +173,26 @@ def _declare(L):
         "sdsp_duc_execute_block": (i, [vp, vp, sz, vp]),
         "sdsp_duc_execute_block_device": (i, [vp, vp, sz, vp, vp]),
         "sdsp_duc_synchronize": (i, [vp]),
+        # rational resampler (M/D polyphase FIR, only kept outputs computed)
+        "sdsp_resamp_create": (i, [vpp, i, vp, sz, sz, sz, i]),
+        "sdsp_resamp_destroy": (None, [vp]),
+        "sdsp_resamp_clone": (i, [vp, vpp]),
+        "sdsp_resamp_reset": (i, [vp]),
+        "sdsp_resamp_set_channels": (i, [vp, sz]),
+        "sdsp_resamp_set_algo": (i, [vp, i]),
+        "sdsp_resamp_get_algo": (i, [vp]),
+        "sdsp_resamp_set_tuning": (i, [vp, i, i]),
+        "sdsp_resamp_interpolation": (sz, [vp]),
+        "sdsp_resamp_decimation": (sz, [vp]),
+        "sdsp_resamp_subfilter_len": (sz, [vp]),
+        "sdsp_resamp_get_phase": (i, [vp, szp]),
+        "sdsp_resamp_set_phase": (i, [vp, sz]),
+        "sdsp_resamp_output_count": (sz, [vp, sz]),
+        "sdsp_resamp_execute_block": (i, [vp, vp, sz, vp, szp]),
+        "sdsp_resamp_execute_block_device": (i, [vp, vp, sz, vp, szp, vp]),
+        "sdsp_resamp_info": (i, [vp, C.POINTER(i), szp]),
+        "sdsp_resamp_synchronize": (i, [vp]),
+        "sdsp_resamp_count": (i, [sz, sz, sz, sz, szp, szp]),
         "sdsp_synth_f32_device": (i, [vp, C.c_uint64, C.c_uint64, C.c_uint64, sz, vp]),
         "sdsp_bandwidth_copy_device": (i, [vp, vp, sz, vp]),
         "sdsp_firdes_kaiser": (i, [sz, d, d, d, dp]),

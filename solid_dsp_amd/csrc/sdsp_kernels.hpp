@@ -244,6 +244,32 @@ struct DucArgs {
     bool down;
 };
 hipError_t launch_duc(int dtype, const DucArgs& d, hipStream_t s);
+// Rational resampler (kern_resamp.hip): the interpolator's stream z[u] = sum_{i<K} cb[u % M][i] ext(u / M - i)
+// taken at u_k = (k + 1) D - 1 - c, k < n_out; only those dot products are computed.
+constexpr int kResampStaged = 1, kResampPerOutput = 2, kResampBranch = 3;
+struct ResampArgs {
+    const void* x;     // [channels][n]
+    const void* hist;  // [channels][H] oldest first, as PfbArgs
+    const void* cb;    // [M][K]
+    void* y;           // [channels][n_out]
+    size_t n, n_out, channels;
+    int K, M, H;
+    size_t D, c;       // decimation, phase counter before the call (c < D)
+    bool exact;
+    int kernel;        // SDSP_TUNE_RESAMP_KERNEL: 0 automatic, or a kResamp* value
+};
+// which kernel a shape runs on and how it is tiled: a function of the shape alone, never of n
+struct ResampPlan {
+    int kernel;       // kResampStaged / kResampPerOutput / kResampBranch
+    size_t tile;      // outputs per workgroup
+    int T;            // staged: outputs per workgroup
+    int A, R, step;   // branch: lanes, outputs per lane, inputs a lane advances per output
+    int S;            // staged and branch: samples of the LDS span
+    bool cb_lds;      // staged: branch table in LDS
+    size_t lds;       // dynamic LDS bytes
+};
+ResampPlan resamp_plan(int dtype, int M, size_t D, int K, int forced);
+hipError_t launch_resamp(int dtype, const ResampArgs& a, hipStream_t s);
 // AGC bank (src/auto_gain_control/mod.rs): state is sdsp_agc_state[channels] in
 // device memory; cplx = Complex<f64> samples, else f64
 // pipe: agc_pipe_kernel for calls it admits (SDSP_TUNE_AGC_KERNEL 0), else agc_kernel
