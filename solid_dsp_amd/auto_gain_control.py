@@ -19,6 +19,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._handle import Handle
 
 
 class AGCErrorCode(enum.IntEnum):  # :49-56
@@ -50,18 +51,14 @@ def _check(rc: int):
     L.check(rc)
 
 
-class AGC:
+class AGC(Handle):
+    _family = "agc"
+
     def __init__(self, channels: int = 1, device: int = 0):  # AGC::new  :136-149
         h = C.c_void_p()
         L.check(L.lib().sdsp_agc_create(C.byref(h), int(channels), int(device)))
         self._h = h
         self.channels = int(channels)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            L.lib().sdsp_agc_destroy(h)
-            self._h = None
 
     def set_tuning(self, key: int, value: int):
         """Kernel-variant knob (L.TUNE_AGC_KERNEL; performance only, same results)."""

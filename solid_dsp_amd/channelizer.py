@@ -12,9 +12,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from ._handle import Handle
 
 
-class Channelizer:
+class Channelizer(Handle):
+    _family = "chan"
+
     def __init__(self, taps, channels: int, sample_dtype=np.complex64, device=0, streams=1):
         sdt = np.dtype(sample_dtype)
         self.dtype = L.RC32 if sdt == np.complex64 else L.RC64
@@ -30,12 +33,6 @@ class Channelizer:
         self.streams = 1
         if streams != 1:
             self.set_streams(streams)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            L.lib().sdsp_chan_destroy(h)
-            self._h = None
 
     def set_tuning(self, key: int, value: int):
         """Kernel-variant knobs (L.TUNE_CHAN_STREAMING, L.TUNE_CHAN_FRAMES_PER_BLOCK, L.TUNE_CHAN_XCD_ORDER;

@@ -75,6 +75,56 @@ int check_device(int device, int* cus) {
     return SDSP_OK;
 }
 
+// ---- FirCore (sdsp_host.hpp): the decimating FIR state of sdsp_fir and sdsp_ddc ----
+hipError_t FirCore::init(int dt, const void* h, size_t len, const void* sc, size_t decimation, int dev) {
+    dtype = dt;
+    algo = default_algo();
+    L = len;
+    M = decimation;
+    const size_t cb = coef_bytes(dt);
+    taps.assign((const unsigned char*)h, (const unsigned char*)h + len * cb);
+    scale.assign((const unsigned char*)sc, (const unsigned char*)sc + cb);
+    std::vector<unsigned char> rev(len * cb);
+    for (size_t i = 0; i < len; ++i) std::memcpy(&rev[i * cb], &taps[(len - 1 - i) * cb], cb);
+    hipError_t e = open(dev);
+    if (e == hipSuccess) e = d_taps_rev.ensure(rev.size());
+    if (e == hipSuccess) e = hipMemcpy(d_taps_rev.p, rev.data(), rev.size(), hipMemcpyHostToDevice);
+    return e;
+}
+
+int FirCore::zero_state() {
+    SDSP_TRY(fence.wait(), "wait for queued work");
+    SDSP_TRY(hist.reset(hist_bytes(), stream), "zero history");
+    ci = 0;
+    return quiesce();
+}
+
+int FirCore::read_hist(void* host) const {
+    if (int st = quiesce()) return st;
+    if (hist_bytes() && host) SDSP_TRY(hipMemcpy(host, hist.front(), hist_bytes(), hipMemcpyDeviceToHost), "get state");
+    return SDSP_OK;
+}
+
+int FirCore::write_hist(const void* host) {
+    if (int st = quiesce()) return st;
+    if (hist_bytes() && host) SDSP_TRY(hipMemcpy(hist.front(), host, hist_bytes(), hipMemcpyHostToDevice), "set state");
+    return SDSP_OK;
+}
+
+int FirCore::copy_state_to(FirCore* c) const {
+    c->algo = algo;
+    c->decim_seg = decim_seg;
+    if (channels != 1) {
+        c->channels = channels;
+        if (int st = c->zero_state()) return st;
+    }
+    if (int st = quiesce()) return st;
+    if (hist_bytes())
+        SDSP_TRY(hipMemcpy(c->hist.front(), hist.front(), hist_bytes(), hipMemcpyDeviceToDevice), "clone state");
+    c->ci = ci;
+    return SDSP_OK;
+}
+
 }  // namespace sdsp
 
 using namespace sdsp;
@@ -113,16 +163,10 @@ struct FirOls {
     }
 };
 
-struct sdsp_fir : HandleCore {
-    int dtype = 0, cus = 256;
+// (taps, delay line, phase and algorithm: FirCore, sdsp_host.hpp)
+struct sdsp_fir : FirCore {
+    int cus = 256;
     mutable unsigned long long device_ops = 0;  // sdsp_fir_device_ops
-    size_t L = 0, M = 1, channels = 1;
-    std::vector<unsigned char> taps;   // original order (host copy for coefficients / design queries)
-    std::vector<unsigned char> scale;  // one Coef
-    DevBuf d_taps_rev;                 // cr[i] = h[L-1-i]  (DotProduct REVERSE, dot_product/mod.rs:73-81)
-    PingPong hist;                     // [channels][L-1] oldest first
-    size_t ci = 0;                     // DecimatingFIRFilter::current_item (decim.rs:7)
-    int algo = SDSP_ALGO_EXACT;        // reference-order kernel unless the caller opts in (sdsp.h)
     HostMapped step_out;  // per-sample execute on the device: output at [0, 16), completion flag at [16, 20)
     unsigned step_seq = 0;
     // host delay line for per-sample calls and small host blocks (runtime_host_step below):
@@ -133,8 +177,7 @@ struct sdsp_fir : HandleCore {
     bool dev_stale = false;   // the host consumed samples after hist.front() was last written
     int host_step = 1;        // SDSP_TUNE_HOST_STEP
     size_t host_macs = 1u << 16;  // host blocks: n * L up to this many multiply-adds
-    int decim_seg = 0;  // outputs per lane group of the polyphase decimator (0 = auto)
-    FirOls ols;         // overlap-save plan
+    FirOls ols;                   // overlap-save plan
 };
 
 bool FirOls::is_real(const sdsp_fir* h) { return h->dtype == SDSP_RR32; }
@@ -237,10 +280,7 @@ int FirOls::run(sdsp_fir* h, const void* d_in, const void* hist, void* d_out, si
 namespace {
 
 int fir_alloc_state(sdsp_fir* h) {
-    SDSP_TRY(h->fence.wait(), "wait for queued work");
-    SDSP_TRY(h->hist.reset(h->channels * (h->L - 1) * sample_bytes(h->dtype), h->stream), "zero history");
-    h->ci = 0;
-    if (int st = h->quiesce()) return st;
+    if (int st = h->zero_state()) return st;
     const size_t lm1 = h->L - 1, sb = sample_bytes(h->dtype);
     h->hbuf.assign(2 * lm1 * sb, 0);  // the zeroed window, both copies
     h->hpos = 0;
@@ -261,11 +301,6 @@ int fir_resolve_algo(const sdsp_fir* h, size_t n) {
     if (FirOls::is_short(h) && !FirOls::is_real(h) && n >= (size_t)(1 << 16)) return SDSP_ALGO_FFT;
     if (FirOls::is_long(h) && n >= kOlsLongAutoMin) return SDSP_ALGO_FFT;
     return SDSP_ALGO_EXACT;
-}
-// AUTO on a decimating handle: the fused multiply-add kernels for long 32-bit blocks (n inputs)
-static int decim_resolve_algo(const sdsp_fir* h, size_t n) {
-    if (h->algo != SDSP_ALGO_AUTO) return h->algo;
-    return h->dtype <= SDSP_CC32 && n >= (size_t)(1 << 16) ? SDSP_ALGO_FMA : SDSP_ALGO_EXACT;
 }
 
 int fir_create_common(sdsp_fir** out, int dtype, const void* taps, size_t len, const void* scale, size_t M,
@@ -292,25 +327,9 @@ int fir_create_common(sdsp_fir** out, int dtype, const void* taps, size_t len, c
     if (st) return st;
     DeviceGuard g(device);
     sdsp_fir* h = new sdsp_fir();
-    h->dtype = dtype;
-    h->algo = default_algo();
     h->cus = cus;
-    h->L = len;
-    h->M = M;
-    const size_t cb = coef_bytes(dtype);
-    h->taps.assign((const unsigned char*)taps, (const unsigned char*)taps + len * cb);
-    h->scale.assign((const unsigned char*)scale, (const unsigned char*)scale + cb);
-    std::vector<unsigned char> rev(len * cb);
-    for (size_t i = 0; i < len; ++i) std::memcpy(&rev[i * cb], &h->taps[(len - 1 - i) * cb], cb);
-    hipError_t e = h->open(device);
-    if (e == hipSuccess) e = h->d_taps_rev.ensure(rev.size());
-    if (e == hipSuccess) e = hipMemcpy(h->d_taps_rev.p, rev.data(), rev.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        st = device_status(e, "fir create");
-        sdsp_fir_destroy(h);
-        return st;
-    }
-    st = fir_alloc_state(h);
+    st = device_status(h->init(dtype, taps, len, scale, M, device), "fir create");
+    if (!st) st = fir_alloc_state(h);
     if (st) {
         sdsp_fir_destroy(h);
         return st;
@@ -619,23 +638,20 @@ int sdsp_fir_clone(const sdsp_fir* h, sdsp_fir** out) {
     if (st) return st;
     sdsp_fir* c = *out;
     DeviceGuard g(h->device);
-    c->algo = h->algo;
-    if (h->channels != 1) {
-        st = sdsp_fir_set_channels(c, h->channels);
-        if (st) return st;
-    }
     c->ols.copy_knobs_from(h->ols);
-    c->decim_seg = h->decim_seg;
-    const size_t hb = h->channels * (h->L - 1) * sample_bytes(h->dtype);
-    st = h->quiesce();
-    if (!st) st = host_flush(h);
-    if (st) return st;
-    if (hb) SDSP_TRY(hipMemcpy(c->hist.front(), h->hist.front(), hb, hipMemcpyDeviceToDevice), "clone state");
-    c->ci = h->ci;
     c->host_step = h->host_step;
     c->host_macs = h->host_macs;
+    // the device history has to be the newest state before it is copied; the clone reads its own
+    // host window back when it needs one
+    st = h->quiesce();
+    if (!st) st = host_flush(h);
+    if (!st) st = h->copy_state_to(c);
     c->host_valid = false;
-    return SDSP_OK;
+    if (st) {  // a failure leaves the caller no handle to destroy
+        sdsp_fir_destroy(c);
+        *out = nullptr;
+    }
+    return st;
 }
 
 int sdsp_fir_set_scale(sdsp_fir* h, const void* scale) {
@@ -667,12 +683,7 @@ int sdsp_fir_coefficients(const sdsp_fir* h, void* out) {
     return SDSP_OK;
 }
 
-size_t sdsp_fir_output_count(const sdsp_fir* h, size_t n) {
-    if (!h) return 0;
-    if (h->M == 1) return n;
-    const size_t j0 = (h->M - 1 - h->ci) % h->M;  // first input index whose push wraps the phase to 0
-    return j0 < n ? (n - 1 - j0) / h->M + 1 : 0;
-}
+size_t sdsp_fir_output_count(const sdsp_fir* h, size_t n) { return h ? h->output_count(n) : 0; }
 
 int sdsp_fir_execute_block_device(sdsp_fir* h, const void* d_in, size_t n, void* d_out, size_t* n_out,
                                   void* stream) {
@@ -705,10 +716,8 @@ int sdsp_fir_execute_block_device(sdsp_fir* h, const void* d_in, size_t n, void*
             SDSP_TRY(launch_fir_direct(h->dtype, a, s), "fir direct");
         }
     } else {
-        const size_t j0 = (h->M - 1 - h->ci) % h->M;
-        const int algo = decim_resolve_algo(h, n) == SDSP_ALGO_FMA ? SDSP_ALGO_FMA : SDSP_ALGO_EXACT;
         FirArgs a{d_in, hist, h->d_taps_rev.p, h->scale.data(), d_out, n, nout, h->channels, (int)h->L, (int)h->M,
-                  j0, algo != SDSP_ALGO_FMA};
+                  h->j0(), h->decim_algo(n) != SDSP_ALGO_FMA};
         a.seg = h->decim_seg;
         SDSP_TRY(launch_decim_direct(h->dtype, a, s), "decim direct");
         h->ci = (h->ci + n) % h->M;
@@ -779,17 +788,17 @@ int sdsp_fir_reset(sdsp_fir* h) {
     return fir_alloc_state(h);
 }
 
-size_t sdsp_fir_state_len(const sdsp_fir* h) { return h ? h->channels * (h->L - 1) : 0; }
+size_t sdsp_fir_state_len(const sdsp_fir* h) { return h ? h->state_len() : 0; }
 
 int sdsp_fir_get_state(const sdsp_fir* h, void* hist, size_t* phase) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     DeviceGuard g(h->device);
-    const size_t hb = h->channels * (h->L - 1) * sample_bytes(h->dtype);
-    if (int st = h->quiesce()) return st;
     if (h->dev_stale) {  // the host window is the newer one
-        if (hb && hist) std::memcpy(hist, h->hbuf.data() + h->hpos * sample_bytes(h->dtype), hb);
-    } else if (hb && hist) {
-        SDSP_TRY(hipMemcpy(hist, h->hist.front(), hb, hipMemcpyDeviceToHost), "get state");
+        if (int st = h->quiesce()) return st;
+        if (h->hist_bytes() && hist)
+            std::memcpy(hist, h->hbuf.data() + h->hpos * sample_bytes(h->dtype), h->hist_bytes());
+    } else if (int st = h->read_hist(hist)) {
+        return st;
     }
     if (phase) *phase = h->ci;
     return SDSP_OK;
@@ -798,9 +807,7 @@ int sdsp_fir_get_state(const sdsp_fir* h, void* hist, size_t* phase) {
 int sdsp_fir_set_state(sdsp_fir* h, const void* hist, size_t phase) {
     if (!h || phase >= h->M) return SDSP_E_INVALID_ARGUMENT;
     DeviceGuard g(h->device);
-    const size_t hb = h->channels * (h->L - 1) * sample_bytes(h->dtype);
-    if (int st = h->quiesce()) return st;
-    if (hb && hist) SDSP_TRY(hipMemcpy(h->hist.front(), hist, hb, hipMemcpyHostToDevice), "set state");
+    if (int st = h->write_hist(hist)) return st;
     h->ci = phase;
     h->dev_stale = false;
     h->host_valid = false;  // re-read on the next host step
@@ -997,32 +1004,16 @@ int sdsp_pfb_set_channels(sdsp_pfb* h, size_t channels) {
 int sdsp_pfb_execute_block_device(sdsp_pfb* h, const void* d_in, size_t n, void* d_out, void* stream) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     if (n == 0) return SDSP_OK;
-    DeviceGuard g(h->device);
-    hipStream_t s = pick(stream, h->stream);
-    const size_t sb = sample_bytes(h->dtype);
-    if (ranges_overlap(d_in, h->channels * n * sb, d_out, h->channels * n * h->M * sb)) {
-        set_error("input and output blocks overlap (in-place filtering is not supported)");
-        return SDSP_E_INVALID_ARGUMENT;
-    }
-    // work queued on another stream (the fence) reads or writes the window this launch uses
-    SDSP_TRY(h->fence.order_before(s), "order after queued work");
-    PfbArgs a{d_in, h->hist.front(), h->d_cb.p, d_out, n, h->channels, (int)h->K, (int)h->M, (int)h->K,
-              h->algo != SDSP_ALGO_FMA};
-    SDSP_TRY(launch_pfb(h->dtype, a, s), "pfb");
-    SDSP_TRY(launch_hist_update(h->dtype, d_in, h->hist.front(), h->hist.back(), n, (int)h->K,
-                                h->channels, s),
-             "window update");
-    h->hist.flip();
-    SDSP_TRY(h->fence.record(s), "record fence");
-    return SDSP_OK;
+    const PfbArgs a{d_in, h->hist.front(), h->d_cb.p, d_out, n, h->channels, (int)h->K, (int)h->M, (int)h->K,
+                    h->algo != SDSP_ALGO_FMA};
+    return h->block_device(d_in, n, d_out, n * h->M, stream, "pfb",
+                           [&](hipStream_t s) { return launch_pfb(h->dtype, a, s); });
 }
 
 int sdsp_pfb_execute_block(sdsp_pfb* h, const void* in, size_t n, void* out) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     if (n == 0) return SDSP_OK;
-    DeviceGuard g(h->device);
-    const size_t bytes = h->channels * n * sample_bytes(h->dtype);
-    return h->staged(in, bytes, out, bytes * h->M, [&](const void* d_in, void* d_out, hipStream_t s) {
+    return h->block_host(in, n, out, n * h->M, [&](const void* d_in, void* d_out, hipStream_t s) {
         return sdsp_pfb_execute_block_device(h, d_in, n, d_out, s);
     });
 }

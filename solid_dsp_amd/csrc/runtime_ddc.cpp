@@ -1,13 +1,10 @@
 // C-ABI runtime of the digital down-converter (include/sdsp.h, sdsp_ddc_*): a decimating FIR
 // whose input passes through the NCO's mix-down on the kernels' load path (kern_ddc.hip).  The
-// handle owns what the two reference objects own: the decimator's reversed taps, delay line
-// (ping-pong, mixed samples) and phase, and the oscillator's u32 phase and frequency registers
-// (host state, as in sdsp_nco) with its sine table on the device.  A block object: no per-sample
-// push and no host-step path.
+// handle is what the two reference objects are: the decimator's state (FirCore, sdsp_host.hpp:
+// reversed taps, ping-pong delay line of mixed samples, phase, algorithm) shared with sdsp_fir,
+// and the oscillator (Oscillator, host registers as in sdsp_nco) with its sine table on the
+// device and the mixing direction.  A block object: no per-sample push and no host-step path.
 #include <hip/hip_runtime.h>
-
-#include <cstring>
-#include <vector>
 
 #include "sdsp.h"
 #include "sdsp_host.hpp"
@@ -15,39 +12,11 @@
 
 using namespace sdsp;
 
-struct sdsp_ddc : HandleCore {
-    int dtype = SDSP_RC32;
-    size_t L = 0, M = 1, channels = 1;
-    std::vector<unsigned char> taps;   // original order (clone)
-    std::vector<unsigned char> scale;  // one Coef
-    DevBuf d_taps_rev;                 // cr[i] = h[L-1-i]
-    PingPong hist;                     // [channels][L-1] mixed samples, oldest first
-    size_t ci = 0;                     // DecimatingFIRFilter::current_item
-    int algo = SDSP_ALGO_EXACT;
-    int decim_seg = 0;                 // SDSP_TUNE_DECIM_SEG
-    uint32_t theta = 0, delta_theta = 0;  // NCO registers (src/nco/mod.rs:27-34)
+struct sdsp_ddc : FirCore {
+    Oscillator osc;
     bool down = true;
-    DevBuf d_table;                    // 1024-entry f64 sine table
+    DevBuf d_table;  // 1024-entry f64 sine table
 };
-
-namespace {
-
-int ddc_alloc_state(sdsp_ddc* h) {
-    SDSP_TRY(h->fence.wait(), "wait for queued work");
-    SDSP_TRY(h->hist.reset(h->channels * (h->L - 1) * sample_bytes(h->dtype), h->stream), "zero history");
-    h->ci = 0;
-    return h->quiesce();
-}
-
-// AUTO: the fused multiply-add kernels for long 32-bit blocks (n inputs), as the decimator
-int ddc_resolve_algo(const sdsp_ddc* h, size_t n) {
-    if (h->algo != SDSP_ALGO_AUTO) return h->algo;
-    return h->dtype <= SDSP_CC32 && n >= (size_t)(1 << 16) ? SDSP_ALGO_FMA : SDSP_ALGO_EXACT;
-}
-
-size_t hist_bytes(const sdsp_ddc* h) { return h->channels * (h->L - 1) * sample_bytes(h->dtype); }
-
-}  // namespace
 
 extern "C" {
 
@@ -71,28 +40,10 @@ int sdsp_ddc_create(sdsp_ddc** out, int dtype, const void* taps, size_t len, con
     if (st) return st;
     DeviceGuard g(device);
     sdsp_ddc* h = new sdsp_ddc();
-    h->dtype = dtype;
-    h->algo = default_algo();
-    h->L = len;
-    h->M = decimation;
-    const size_t cb = coef_bytes(dtype);
-    h->taps.assign((const unsigned char*)taps, (const unsigned char*)taps + len * cb);
-    h->scale.assign((const unsigned char*)scale, (const unsigned char*)scale + cb);
-    std::vector<unsigned char> rev(len * cb);
-    for (size_t i = 0; i < len; ++i) std::memcpy(&rev[i * cb], &h->taps[(len - 1 - i) * cb], cb);
-    double table[1024];
-    nco_sine_table(table);
-    hipError_t e = h->open(device);
-    if (e == hipSuccess) e = h->d_taps_rev.ensure(rev.size());
-    if (e == hipSuccess) e = hipMemcpy(h->d_taps_rev.p, rev.data(), rev.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = h->d_table.ensure(sizeof(table));
-    if (e == hipSuccess) e = hipMemcpy(h->d_table.p, table, sizeof(table), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        st = device_status(e, "ddc create");
-        sdsp_ddc_destroy(h);
-        return st;
-    }
-    st = ddc_alloc_state(h);
+    hipError_t e = h->init(dtype, taps, len, scale, decimation, device);
+    if (e == hipSuccess) e = nco_upload_sine_table(h->d_table);
+    st = device_status(e, "ddc create");
+    if (!st) st = h->zero_state();
     if (st) {
         sdsp_ddc_destroy(h);
         return st;
@@ -109,41 +60,28 @@ int sdsp_ddc_clone(const sdsp_ddc* h, sdsp_ddc** out) {
     if (st) return st;
     sdsp_ddc* c = *out;
     DeviceGuard g(h->device);
-    c->algo = h->algo;
-    c->decim_seg = h->decim_seg;
     c->down = h->down;
-    c->theta = h->theta;
-    c->delta_theta = h->delta_theta;
-    // a failure from here on leaves the caller no handle to destroy
-    auto fail = [&](int code) {
+    c->osc = h->osc;
+    st = h->copy_state_to(c);
+    if (st) {  // a failure leaves the caller no handle to destroy
         sdsp_ddc_destroy(c);
         *out = nullptr;
-        return code;
-    };
-    if (h->channels != 1 && (st = sdsp_ddc_set_channels(c, h->channels))) return fail(st);
-    if ((st = h->quiesce())) return fail(st);
-    const size_t hb = hist_bytes(h);
-    if (hb) {
-        const hipError_t e = hipMemcpy(c->hist.front(), h->hist.front(), hb, hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) return fail(device_status(e, "clone state"));
     }
-    c->ci = h->ci;
-    return SDSP_OK;
+    return st;
 }
 
 int sdsp_ddc_reset(sdsp_ddc* h) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     DeviceGuard g(h->device);
-    h->theta = 0;  // NCO::reset  src/nco/mod.rs:53-56
-    h->delta_theta = 0;
-    return ddc_alloc_state(h);
+    h->osc.reset();
+    return h->zero_state();
 }
 
 int sdsp_ddc_set_channels(sdsp_ddc* h, size_t channels) {
     if (!h || channels == 0) return SDSP_E_INVALID_ARGUMENT;
     DeviceGuard g(h->device);
     h->channels = channels;
-    return ddc_alloc_state(h);
+    return h->zero_state();
 }
 
 int sdsp_ddc_set_algo(sdsp_ddc* h, int algo) {
@@ -164,47 +102,27 @@ int sdsp_ddc_set_direction(sdsp_ddc* h, int up) {
     return SDSP_OK;
 }
 
-// The oscillator's registers are host state read at each launch: a setter between two calls takes
-// effect at the next call's first sample (src/nco/mod.rs:59-86; u32 adds wrap as in release builds)
+// the oscillator's setters (Oscillator, sdsp_host.hpp): in effect from the next call's first sample
 int sdsp_ddc_set_frequency(sdsp_ddc* h, double delta_theta) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->delta_theta = nco_constrain(delta_theta);
-    return SDSP_OK;
+    return h ? h->osc.set_frequency(delta_theta) : SDSP_E_INVALID_ARGUMENT;
 }
 int sdsp_ddc_adjust_frequency(sdsp_ddc* h, double dt) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->delta_theta += nco_constrain(dt);
-    return SDSP_OK;
+    return h ? h->osc.adjust_frequency(dt) : SDSP_E_INVALID_ARGUMENT;
 }
 int sdsp_ddc_set_phase(sdsp_ddc* h, double phi) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->theta = nco_constrain(phi);
-    return SDSP_OK;
+    return h ? h->osc.set_phase(phi) : SDSP_E_INVALID_ARGUMENT;
 }
 int sdsp_ddc_adjust_phase(sdsp_ddc* h, double delta_phi) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->theta += nco_constrain(delta_phi);
-    return SDSP_OK;
+    return h ? h->osc.adjust_phase(delta_phi) : SDSP_E_INVALID_ARGUMENT;
 }
 int sdsp_ddc_get_nco_state(const sdsp_ddc* h, uint32_t* theta, uint32_t* delta_theta) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    if (theta) *theta = h->theta;
-    if (delta_theta) *delta_theta = h->delta_theta;
-    return SDSP_OK;
+    return h ? h->osc.get(theta, delta_theta) : SDSP_E_INVALID_ARGUMENT;
 }
 int sdsp_ddc_set_nco_state(sdsp_ddc* h, uint32_t theta, uint32_t delta_theta) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->theta = theta;
-    h->delta_theta = delta_theta;
-    return SDSP_OK;
+    return h ? h->osc.set(theta, delta_theta) : SDSP_E_INVALID_ARGUMENT;
 }
 
-size_t sdsp_ddc_output_count(const sdsp_ddc* h, size_t n) {
-    if (!h) return 0;
-    if (h->M == 1) return n;
-    const size_t j0 = (h->M - 1 - h->ci) % h->M;  // first input index whose push wraps the phase to 0
-    return j0 < n ? (n - 1 - j0) / h->M + 1 : 0;
-}
+size_t sdsp_ddc_output_count(const sdsp_ddc* h, size_t n) { return h ? h->output_count(n) : 0; }
 
 int sdsp_ddc_execute_block_device(sdsp_ddc* h, const void* d_in, size_t n, void* d_out, size_t* n_out,
                                   void* stream) {
@@ -222,18 +140,15 @@ int sdsp_ddc_execute_block_device(sdsp_ddc* h, const void* d_in, size_t n, void*
     }
     // work queued on another stream (the fence) reads or writes the history this launch uses
     SDSP_TRY(h->fence.order_before(s), "order after queued work");
-    const void* hist = h->hist.front();
-    const size_t j0 = (h->M - 1 - h->ci) % h->M;
-    const bool exact = ddc_resolve_algo(h, n) != SDSP_ALGO_FMA;
-    DdcArgs a{FirArgs{d_in, hist, h->d_taps_rev.p, h->scale.data(), d_out, n, nout, h->channels, (int)h->L,
-                      (int)h->M, j0, exact},
-              (const double*)h->d_table.p, h->theta, h->delta_theta, h->down};
+    DdcArgs a{FirArgs{d_in, h->hist.front(), h->d_taps_rev.p, h->scale.data(), d_out, n, nout, h->channels,
+                      (int)h->L, (int)h->M, h->j0(), h->decim_algo(n) != SDSP_ALGO_FMA},
+              (const double*)h->d_table.p, h->osc.theta, h->osc.delta_theta, h->down};
     a.fir.seg = h->decim_seg;
     SDSP_TRY(launch_ddc(h->dtype, a, s), "ddc");
     SDSP_TRY(launch_ddc_hist(h->dtype, a, h->hist.back(), s), "ddc history update");
     h->hist.flip();
     h->ci = (h->ci + n) % h->M;
-    h->theta += (uint32_t)((uint64_t)n * h->delta_theta);  // n steps, wrapping
+    h->osc.advance(n);
     SDSP_TRY(h->fence.record(s), "record fence");
     return SDSP_OK;
 }
@@ -253,14 +168,12 @@ int sdsp_ddc_execute_block(sdsp_ddc* h, const void* in, size_t n, void* out, siz
                      });
 }
 
-size_t sdsp_ddc_state_len(const sdsp_ddc* h) { return h ? h->channels * (h->L - 1) : 0; }
+size_t sdsp_ddc_state_len(const sdsp_ddc* h) { return h ? h->state_len() : 0; }
 
 int sdsp_ddc_get_state(const sdsp_ddc* h, void* hist, size_t* phase) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     DeviceGuard g(h->device);
-    const size_t hb = hist_bytes(h);
-    if (int st = h->quiesce()) return st;
-    if (hb && hist) SDSP_TRY(hipMemcpy(hist, h->hist.front(), hb, hipMemcpyDeviceToHost), "get state");
+    if (int st = h->read_hist(hist)) return st;
     if (phase) *phase = h->ci;
     return SDSP_OK;
 }
@@ -268,9 +181,7 @@ int sdsp_ddc_get_state(const sdsp_ddc* h, void* hist, size_t* phase) {
 int sdsp_ddc_set_state(sdsp_ddc* h, const void* hist, size_t phase) {
     if (!h || phase >= h->M) return SDSP_E_INVALID_ARGUMENT;
     DeviceGuard g(h->device);
-    const size_t hb = hist_bytes(h);
-    if (int st = h->quiesce()) return st;
-    if (hb && hist) SDSP_TRY(hipMemcpy(h->hist.front(), hist, hb, hipMemcpyHostToDevice), "set state");
+    if (int st = h->write_hist(hist)) return st;
     h->ci = phase;
     return SDSP_OK;
 }

@@ -1,10 +1,11 @@
 // C-ABI runtime of the rational resampler (include/sdsp.h, sdsp_resamp_*): an interpolating FIR
 // whose output is taken every D-th sample, with only the kept dot products computed
 // (kern_resamp.hip).  The handle owns an interpolator handle made by sdsp_interp_create, as the
-// up-converter does (taps, K, zero padding, branch layout, window, algorithm, and the HandleCore
-// every call here runs on), and adds the decimation D, the phase counter c (host state, the
-// reference decimator's counter applied to the interpolated stream) and the kernel knob.  A block
-// object: no per-sample entry point, no scale, no window get / set.
+// up-converter does (taps, K, zero padding, branch layout, window, algorithm, the block path
+// sdsp_pfb::block_device and the HandleCore every call here runs on), and adds the decimation D,
+// the phase counter c (host state, the reference decimator's counter applied to the interpolated
+// stream) and the kernel knob.  A block object: no per-sample entry point, no scale, no window
+// get / set.
 #include <hip/hip_runtime.h>
 
 #include "sdsp.h"
@@ -150,23 +151,12 @@ int sdsp_resamp_execute_block_device(sdsp_resamp* h, const void* d_in, size_t n,
         set_error("resampler block: n * interpolation does not fit 63 bits");
         return SDSP_E_INVALID_ARGUMENT;
     }
-    DeviceGuard g(f->device);
-    hipStream_t s = pick(stream, f->stream);
-    const size_t sb = sample_bytes(f->dtype);
-    if (ranges_overlap(d_in, f->channels * n * sb, d_out, f->channels * no * sb)) {
-        set_error("input and output blocks overlap (in-place filtering is not supported)");
-        return SDSP_E_INVALID_ARGUMENT;
-    }
-    // work queued on another stream (the fence) reads or writes the window this launch uses
-    SDSP_TRY(f->fence.order_before(s), "order after queued work");
     const ResampArgs a{d_in, f->hist.front(), f->d_cb.p, d_out, n, no, f->channels, (int)f->K, (int)f->M, (int)f->K,
                        h->D, h->c, f->algo != SDSP_ALGO_FMA, h->kernel};
-    SDSP_TRY(launch_resamp(f->dtype, a, s), "resamp");  // nothing when no == 0
-    SDSP_TRY(launch_hist_update(f->dtype, d_in, f->hist.front(), f->hist.back(), n, (int)f->K, f->channels, s),
-             "window update");
-    f->hist.flip();
+    if (int st = f->block_device(d_in, n, d_out, no, stream, "resamp",  // (launches nothing when no == 0)
+                                 [&](hipStream_t s) { return launch_resamp(f->dtype, a, s); }))
+        return st;
     h->c = next;
-    SDSP_TRY(f->fence.record(s), "record fence");
     if (n_out) *n_out = no;
     return SDSP_OK;
 }
@@ -175,13 +165,10 @@ int sdsp_resamp_execute_block(sdsp_resamp* h, const void* in, size_t n, void* ou
     if (n_out) *n_out = 0;
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     if (n == 0) return SDSP_OK;
-    sdsp_pfb* f = h->f;
-    DeviceGuard g(f->device);
-    const size_t sb = f->channels * sample_bytes(f->dtype);
-    return f->staged(in, n * sb, out, sdsp_resamp_output_count(h, n) * sb,
-                     [&](const void* d_in, void* d_out, hipStream_t s) {
-                         return sdsp_resamp_execute_block_device(h, d_in, n, d_out, n_out, s);
-                     });
+    return h->f->block_host(in, n, out, sdsp_resamp_output_count(h, n),
+                            [&](const void* d_in, void* d_out, hipStream_t s) {
+                                return sdsp_resamp_execute_block_device(h, d_in, n, d_out, n_out, s);
+                            });
 }
 
 int sdsp_resamp_synchronize(sdsp_resamp* h) {

@@ -24,7 +24,7 @@ int hist_dtype(int prec) { return prec == 0 ? SDSP_RC32 : SDSP_RC64; }  // sampl
 }  // namespace
 
 namespace sdsp {
-// nco_constrain()  src/nco/mod.rs:175-187 (the NCO and the down-converter share this copy)
+// nco_constrain()  src/nco/mod.rs:175-187 (the NCO and the two converters share this copy)
 uint32_t nco_constrain(double theta) {
     const double d = theta / (2.0 * M_PI);
     double f = d - std::trunc(d);  // f64::fract
@@ -34,6 +34,12 @@ uint32_t nco_constrain(double theta) {
 // NCO::new's sine table  src/nco/mod.rs:36-50
 void nco_sine_table(double* table) {
     for (int i = 0; i < 1024; ++i) table[i] = std::sin(2.0 * M_PI * (double)i / 1024.0);
+}
+hipError_t nco_upload_sine_table(DevBuf& d) {
+    double table[1024];
+    nco_sine_table(table);
+    const hipError_t e = d.ensure(sizeof(table));
+    return e != hipSuccess ? e : hipMemcpy(d.p, table, sizeof(table), hipMemcpyHostToDevice);
 }
 }  // namespace sdsp
 
@@ -207,11 +213,11 @@ int sdsp_acorr_synchronize(sdsp_acorr* h) {
 // (records no fence: calls share only the read-only table)
 struct sdsp_nco : HandleCore {
     int cus = 256;
-    uint32_t theta = 0, delta_theta = 0;
+    Oscillator osc;
     double alpha = 0.1, beta = 0.0;
-    double table[1024];
+    double table[1024];  // host copy for sincos()
     DevBuf d_table;
-    size_t index() const { return (size_t)(((uint32_t)(theta + (1u << 21)) >> 22) & 0x3ffu); }  // :99-101
+    size_t index() const { return (size_t)(((uint32_t)(osc.theta + (1u << 21)) >> 22) & 0x3ffu); }  // :99-101
 };
 
 extern "C" {
@@ -233,8 +239,7 @@ int sdsp_nco_create(sdsp_nco** out, int device) {  // NCO::new  src/nco/mod.rs:3
         set_error("hipStreamCreate failed");
         return SDSP_E_DEVICE;
     }
-    if (h->d_table.ensure(sizeof(h->table)) != hipSuccess ||
-        hipMemcpy(h->d_table.p, h->table, sizeof(h->table), hipMemcpyHostToDevice) != hipSuccess) {
+    if (nco_upload_sine_table(h->d_table) != hipSuccess) {
         sdsp_nco_destroy(h);
         set_error("NCO table upload failed");
         return SDSP_E_DEVICE;
@@ -247,43 +252,34 @@ void sdsp_nco_destroy(sdsp_nco* h) { destroy_handle(h); }
 
 int sdsp_nco_reset(sdsp_nco* h) {  // :53-56
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->theta = 0;
-    h->delta_theta = 0;
+    h->osc.reset();
     return SDSP_OK;
 }
 uint32_t sdsp_nco_constrain(double theta) { return nco_constrain(theta); }  // :175-187
 int sdsp_nco_set_frequency(sdsp_nco* h, double dtheta) {  // :59-61
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->delta_theta = nco_constrain(dtheta);
-    return SDSP_OK;
+    return h ? h->osc.set_frequency(dtheta) : SDSP_E_INVALID_ARGUMENT;
 }
-int sdsp_nco_adjust_frequency(sdsp_nco* h, double dt) {  // :64-66 (u32 add wraps in release builds)
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->delta_theta += nco_constrain(dt);
-    return SDSP_OK;
+int sdsp_nco_adjust_frequency(sdsp_nco* h, double dt) {  // :64-66
+    return h ? h->osc.adjust_frequency(dt) : SDSP_E_INVALID_ARGUMENT;
 }
 // get_frequency (:69-76): (delta_theta as u64 / 2^32) is integer division, always 0 for a u32
 double sdsp_nco_get_frequency(const sdsp_nco* h) {
     if (!h) return 0.0;
-    const double dt = (double)((uint64_t)h->delta_theta / (1ULL << 32)) * 2.0 * M_PI;
+    const double dt = (double)((uint64_t)h->osc.delta_theta / (1ULL << 32)) * 2.0 * M_PI;
     return dt > M_PI ? dt - 2.0 * M_PI : dt;
 }
 int sdsp_nco_set_phase(sdsp_nco* h, double phi) {  // :79-81
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->theta = nco_constrain(phi);
-    return SDSP_OK;
+    return h ? h->osc.set_phase(phi) : SDSP_E_INVALID_ARGUMENT;
 }
 int sdsp_nco_adjust_phase(sdsp_nco* h, double dphi) {  // :84-86
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->theta += nco_constrain(dphi);
-    return SDSP_OK;
+    return h ? h->osc.adjust_phase(dphi) : SDSP_E_INVALID_ARGUMENT;
 }
 double sdsp_nco_get_phase(const sdsp_nco* h) {  // :89-91 (integer division as get_frequency)
-    return h ? (double)((uint64_t)h->theta / (1ULL << 32)) * 2.0 * M_PI : 0.0;
+    return h ? (double)((uint64_t)h->osc.theta / (1ULL << 32)) * 2.0 * M_PI : 0.0;
 }
 int sdsp_nco_step(sdsp_nco* h) {  // :94-96
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->theta += h->delta_theta;
+    h->osc.advance(1);
     return SDSP_OK;
 }
 int sdsp_nco_sincos(const sdsp_nco* h, double* sin_cos) {  // :104-117
@@ -304,21 +300,14 @@ int sdsp_nco_set_internal_pll_bandwidth(sdsp_nco* h, double bandwidth) {  // :12
 }
 int sdsp_nco_pll_step(sdsp_nco* h, double delta_phi) {  // :135-138
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->delta_theta += nco_constrain(delta_phi * h->alpha);
-    h->theta += nco_constrain(delta_phi * h->beta);
-    return SDSP_OK;
+    h->osc.adjust_frequency(delta_phi * h->alpha);
+    return h->osc.adjust_phase(delta_phi * h->beta);
 }
 int sdsp_nco_get_state(const sdsp_nco* h, uint32_t* theta, uint32_t* delta_theta) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    if (theta) *theta = h->theta;
-    if (delta_theta) *delta_theta = h->delta_theta;
-    return SDSP_OK;
+    return h ? h->osc.get(theta, delta_theta) : SDSP_E_INVALID_ARGUMENT;
 }
 int sdsp_nco_set_state(sdsp_nco* h, uint32_t theta, uint32_t delta_theta) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    h->theta = theta;
-    h->delta_theta = delta_theta;
-    return SDSP_OK;
+    return h ? h->osc.set(theta, delta_theta) : SDSP_E_INVALID_ARGUMENT;
 }
 
 // mix_up_block / mix_down_block (:153-172) as the per-sample loop they spell out:
@@ -327,10 +316,10 @@ int sdsp_nco_mix_block_device(sdsp_nco* h, int down, int precision, const void* 
                               void* stream) {
     if (!h || (precision != 0 && precision != 1) || (n && (!d_in || !d_out))) return SDSP_E_INVALID_ARGUMENT;
     DeviceGuard g(h->device);
-    SDSP_TRY(launch_nco_mix(precision, down != 0, d_in, d_out, n, (const double*)h->d_table.p, h->theta, h->delta_theta,
-                         h->cus, pick(stream, h->stream)),
+    SDSP_TRY(launch_nco_mix(precision, down != 0, d_in, d_out, n, (const double*)h->d_table.p, h->osc.theta,
+                         h->osc.delta_theta, h->cus, pick(stream, h->stream)),
           "nco mix");
-    h->theta += (uint32_t)((uint64_t)n * h->delta_theta);  // n steps, wrapping
+    h->osc.advance(n);
     return SDSP_OK;
 }
 

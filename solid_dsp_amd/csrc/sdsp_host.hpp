@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "sdsp.h"
+#include "sdsp_kernels.hpp"
 
 namespace sdsp {
 
@@ -30,16 +31,23 @@ void set_error(const std::string& msg);
 // the algorithm new FIR-type and IIR handles start on (sdsp_set_default_algo; SDSP_DEFAULT_ALGO)
 int default_algo();
 int device_status(hipError_t e, const char* what);
-#define SDSP_TRY(expr, what)                                  \
-    do {                                                      \
-        hipError_t _e = (expr);                               \
-        if (_e != hipSuccess) return device_status(_e, what); \
+#define SDSP_TRY(expr, what)                                        \
+    do {                                                            \
+        hipError_t _e = (expr);                                     \
+        if (_e != hipSuccess) return sdsp::device_status(_e, what); \
     } while (0)
 
 // the NCO's phase arithmetic (runtime_rx.cpp): constrain() of an angle to the u32 phase register,
 // and the 1024-entry f64 sine table of NCO::new
 uint32_t nco_constrain(double theta);
 void nco_sine_table(double* table);
+
+// [a, a + na) and [b, b + nb) overlap (byte ranges)
+inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    if (!na || !nb) return false;
+    const auto pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return pa < pb + nb && pb < pa + na;
+}
 
 // SDSP_OK when `device` is a usable gfx950 device, SDSP_E_NO_DEVICE otherwise; *cus (when given)
 // receives its compute-unit count
@@ -285,11 +293,77 @@ template <typename H> void destroy_handle(H* h) {
     delete h;
 }
 
+// The oscillator of the NCO, the down-converter and the up-converter: the two u32 registers of
+// struct NCO (src/nco/mod.rs:27-34) as host state, read at each launch, so a setter between two
+// calls takes effect at the next call's first sample (:53-86; u32 adds wrap as in release builds)
+// The setters return SDSP_OK: the exported functions forward to them.
+struct Oscillator {
+    uint32_t theta = 0, delta_theta = 0;
+    void reset() { theta = delta_theta = 0; }
+    int set_frequency(double dtheta) { return set(theta, nco_constrain(dtheta)); }
+    int adjust_frequency(double dt) { return set(theta, delta_theta + nco_constrain(dt)); }
+    int set_phase(double phi) { return set(nco_constrain(phi), delta_theta); }
+    int adjust_phase(double dphi) { return set(theta + nco_constrain(dphi), delta_theta); }
+    // `steps` calls of NCO::step (:94-96); the product wraps mod 2^32 as the single adds would
+    void advance(uint64_t steps) { theta += (uint32_t)(steps * delta_theta); }
+    int get(uint32_t* t, uint32_t* dt) const {
+        if (t) *t = theta;
+        if (dt) *dt = delta_theta;
+        return SDSP_OK;
+    }
+    int set(uint32_t t, uint32_t dt) {
+        theta = t;
+        delta_theta = dt;
+        return SDSP_OK;
+    }
+};
+
+// nco_sine_table() into `d` on the current device (runtime_rx.cpp)
+hipError_t nco_upload_sine_table(DevBuf& d);
+
+// What a decimating FIR is on the device, whoever feeds it: taps, delay line, decimation phase
+// and the kernel choice.  sdsp_fir (runtime.cpp) adds the host step and overlap-save around it,
+// sdsp_ddc (runtime_ddc.cpp) the oscillator; the members below (runtime.cpp) serve both alike.
+struct FirCore : HandleCore {
+    int dtype = 0;
+    size_t L = 0, M = 1, channels = 1;
+    std::vector<unsigned char> taps;   // original order (host copy for coefficients / design queries / clone)
+    std::vector<unsigned char> scale;  // one Coef
+    DevBuf d_taps_rev;                 // cr[i] = h[L-1-i]  (DotProduct REVERSE, dot_product/mod.rs:73-81)
+    PingPong hist;                     // [channels][L-1] oldest first
+    size_t ci = 0;                     // DecimatingFIRFilter::current_item (decim.rs:7)
+    int algo = SDSP_ALGO_EXACT;        // reference-order kernel unless the caller opts in (sdsp.h)
+    int decim_seg = 0;                 // outputs per lane group of the polyphase decimator (0 = auto)
+
+    size_t state_len() const { return channels * (L - 1); }
+    size_t hist_bytes() const { return state_len() * sample_bytes(dtype); }
+    size_t j0() const { return (M - 1 - ci) % M; }  // first input index whose push wraps the phase to 0
+    size_t output_count(size_t n) const {
+        if (M == 1) return n;
+        return j0() < n ? (n - 1 - j0()) / M + 1 : 0;
+    }
+    // AUTO on a decimating handle: the fused multiply-add kernels for long 32-bit blocks (n inputs)
+    int decim_algo(size_t n) const {
+        if (algo != SDSP_ALGO_AUTO) return algo;
+        return dtype <= SDSP_CC32 && n >= (size_t)(1 << 16) ? SDSP_ALGO_FMA : SDSP_ALGO_EXACT;
+    }
+    // validated arguments -> taps and scale stored, the process default algorithm, the stream open
+    // and the reversed taps on `device` (the current one); the state is not yet allocated
+    hipError_t init(int dtype, const void* taps, size_t len, const void* scale, size_t M, int device);
+    int zero_state();  // [channels][L-1] zeros in both halves, phase 0, nothing queued
+    // the device halves of get_state / set_state: after quiesce(), the delay line to / from `host`
+    // (nothing when it is null)
+    int read_hist(void* host) const;
+    int write_hist(const void* host);
+    // `c`, freshly created from this handle's taps: algorithm, knob, channels, delay line and phase
+    int copy_state_to(FirCore* c) const;
+};
+
 }  // namespace sdsp
 
 // Polyphase filterbank / interpolating FIR handle (runtime.cpp).  Defined here because the
-// up-converter (runtime_duc.cpp) is an interpolator handle plus an oscillator and launches its own
-// kernels on the interpolator's coefficients and window.
+// up-converter (runtime_duc.cpp) and the resampler (runtime_resamp.cpp) are an interpolator handle
+// plus their own registers, and launch their own kernels on its coefficients and window.
 struct sdsp_pfb : sdsp::HandleCore {
     int dtype = 0;
     size_t M = 0, K = 0, channels = 1;
@@ -299,15 +373,34 @@ struct sdsp_pfb : sdsp::HandleCore {
     sdsp::DevBuf d_cb;
     sdsp::PingPong hist;  // [channels][K] : the Window(K), oldest first
     int algo = SDSP_ALGO_EXACT;
+
+    // One device block of n inputs and n_out outputs per channel on the caller's stream (or the
+    // handle's): launch(stream) -> hipError_t queues the kernel that reads d_in and hist.front(),
+    // then the window moves on by the n inputs.  `what` names the launch in an error.
+    template <typename Launch>
+    int block_device(const void* d_in, size_t n, void* d_out, size_t n_out, void* user_stream, const char* what,
+                     Launch launch) {
+        sdsp::DeviceGuard g(device);
+        hipStream_t s = sdsp::pick(user_stream, stream);
+        const size_t sb = sdsp::sample_bytes(dtype);
+        if (sdsp::ranges_overlap(d_in, channels * n * sb, d_out, channels * n_out * sb)) {
+            sdsp::set_error("input and output blocks overlap (in-place filtering is not supported)");
+            return SDSP_E_INVALID_ARGUMENT;
+        }
+        // work queued on another stream (the fence) reads or writes the window this launch uses
+        SDSP_TRY(fence.order_before(s), "order after queued work");
+        SDSP_TRY(launch(s), what);
+        SDSP_TRY(sdsp::launch_hist_update(dtype, d_in, hist.front(), hist.back(), n, (int)K, channels, s),
+                 "window update");
+        hist.flip();
+        SDSP_TRY(fence.record(s), "record fence");
+        return SDSP_OK;
+    }
+    // The host-slice twin: [channels][n] in and [channels][n_out] out through the staging buffers,
+    // run(d_in, d_out, stream) being the device entry point
+    template <typename Run> int block_host(const void* in, size_t n, void* out, size_t n_out, Run run) {
+        sdsp::DeviceGuard g(device);
+        const size_t sb = channels * sdsp::sample_bytes(dtype);
+        return staged(in, n * sb, out, n_out * sb, run);
+    }
 };
-
-namespace sdsp {
-
-// [a, a + na) and [b, b + nb) overlap (byte ranges)
-inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    if (!na || !nb) return false;
-    const auto pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + nb && pb < pa + na;
-}
-
-}  // namespace sdsp

@@ -19,94 +19,33 @@ import ctypes as C
 
 import numpy as np
 
+from . import _handle as H
 from . import _lib as L
-from .filter.fir import _coef_array, _default_sample
 
 
-class DDC:
+class DDC(H.Oscillator, H.FirHandle):
+    _family = "ddc"
+
     def __init__(self, taps, scale=1.0, decimation=1, sample_dtype=None, coef_dtype=None, device=0, channels=1,
                  algo=None):
-        c = _coef_array(taps, coef_dtype)
-        if sample_dtype is None:
-            sample_dtype = _default_sample(c.dtype)
-        self.dtype = L.dtype_code(c.dtype, sample_dtype)
-        self.coef_dtype = L.COEF_DTYPE[self.dtype]
-        self.sample_dtype = L.SAMPLE_DTYPE[self.dtype]
+        c = self._coefs(taps, sample_dtype, coef_dtype)
         s = np.array([scale], dtype=self.coef_dtype)
         h = C.c_void_p()
         L.check(L.lib().sdsp_ddc_create(C.byref(h), self.dtype, L.ptr(c), len(c), L.ptr(s), int(decimation),
                                         int(device)))
-        self._h = h
-        self.device = device
-        self.channels = 1
-        if channels != 1:
-            self.set_channels(channels)
-        if algo is not None:  # default: the process default, ALGO_EXACT unless changed
-            self.set_algo(algo)
+        self._adopt(h, device, channels, algo)  # algo None: the process default, ALGO_EXACT unless changed
 
     @classmethod
     def new(cls, taps, scale, decimation, **kw):
         return cls(taps, scale, decimation, **kw)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            L.lib().sdsp_ddc_destroy(h)
-            self._h = None
-
     # ---- configuration -------------------------------------------------
-    def set_channels(self, channels: int):
-        L.check(L.lib().sdsp_ddc_set_channels(self._h, channels))
-        self.channels = channels
-
-    def set_algo(self, algo: int):
-        L.check(L.lib().sdsp_ddc_set_algo(self._h, int(algo)))
-
-    def get_algo(self) -> int:
-        return int(L.lib().sdsp_ddc_get_algo(self._h))
+    set_channels, set_algo, get_algo = H.set_channels, H.set_algo, H.get_algo
+    set_tuning = H.set_tuning  # SDSP_TUNE_DECIM_SEG, the polyphase kernel's group length
 
     def set_direction(self, up: bool):
         """False (default): mix_down; True: mix_up."""
-        L.check(L.lib().sdsp_ddc_set_direction(self._h, 1 if up else 0))
-
-    def set_tuning(self, key: int, value: int):
-        """SDSP_TUNE_DECIM_SEG, the polyphase kernel's group length (performance only)"""
-        L.check(L.lib().sdsp_ddc_set_tuning(self._h, int(key), int(value)))
-
-    def clone(self):
-        h = C.c_void_p()
-        L.check(L.lib().sdsp_ddc_clone(self._h, C.byref(h)))
-        obj = type(self).__new__(type(self))
-        obj.__dict__.update({k: v for k, v in self.__dict__.items() if k != "_h"})
-        obj._h = h
-        return obj
-
-    __copy__ = clone
-
-    def reset(self):
-        L.check(L.lib().sdsp_ddc_reset(self._h))
-
-    # ---- oscillator (NCO setters, src/nco/mod.rs:59-86) -----------------
-    def set_frequency(self, delta_theta: float):
-        L.check(L.lib().sdsp_ddc_set_frequency(self._h, float(delta_theta)))
-
-    def adjust_frequency(self, dt: float):
-        L.check(L.lib().sdsp_ddc_adjust_frequency(self._h, float(dt)))
-
-    def set_phase(self, phi: float):
-        L.check(L.lib().sdsp_ddc_set_phase(self._h, float(phi)))
-
-    def adjust_phase(self, delta_phi: float):
-        L.check(L.lib().sdsp_ddc_adjust_phase(self._h, float(delta_phi)))
-
-    def nco_state(self):
-        """(theta, delta_theta), the raw u32 registers"""
-        th, dt = C.c_uint32(), C.c_uint32()
-        L.check(L.lib().sdsp_ddc_get_nco_state(self._h, C.byref(th), C.byref(dt)))
-        return th.value, dt.value
-
-    def set_nco_state(self, theta: int, delta_theta: int):
-        L.check(L.lib().sdsp_ddc_set_nco_state(self._h, int(theta) & 0xFFFFFFFF, int(delta_theta) & 0xFFFFFFFF))
+        self._call("set_direction", 1 if up else 0)
 
     # ---- delay line -----------------------------------------------------
     def get_state(self):
@@ -127,13 +66,8 @@ class DDC:
 
     def execute_block(self, samples) -> np.ndarray:
         """Host samples (channel-major [channels, n] when channels > 1) -> the decimated outputs."""
-        x = np.ascontiguousarray(samples, dtype=self.sample_dtype)
-        n = x.shape[-1] if x.ndim else 0
-        if self.channels > 1 and (x.ndim != 2 or x.shape[0] != self.channels):
-            raise ValueError("multi-channel input must be [channels, n]")
-        nout = self.output_count(n)
-        y = np.zeros((self.channels, nout), dtype=self.sample_dtype) if self.channels > 1 else \
-            np.zeros(nout, dtype=self.sample_dtype)
+        x, n = self._block_in(samples)
+        y = self._block_out(self.output_count(n))
         got = C.c_size_t(0)
         L.check(L.lib().sdsp_ddc_execute_block(self._h, L.ptr(x) if x.size else None, n,
                                                L.ptr(y) if y.size else None, C.byref(got)))
@@ -147,6 +81,3 @@ class DDC:
         pout = L.device_ptr(d_out, self.sample_dtype, self.channels * self.output_count(n), self.device, "output")
         L.check(L.lib().sdsp_ddc_execute_block_device(self._h, pin, n, pout, C.byref(got), L.stream_handle(stream)))
         return got.value
-
-    def synchronize(self):
-        L.check(L.lib().sdsp_ddc_synchronize(self._h))

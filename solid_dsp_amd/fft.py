@@ -15,6 +15,7 @@ import enum
 import numpy as np
 
 from . import _lib as L
+from ._handle import Handle
 
 
 class FFTDirection(enum.IntEnum):  # src/fft/mod.rs:14-18
@@ -27,7 +28,9 @@ class FFTFlags(enum.IntEnum):  # src/fft/mod.rs:49-53 (planning hint; one plan k
     MEASURE = 1
 
 
-class FFT:
+class FFT(Handle):
+    _family = "fft"
+
     def __init__(self, nfft: int, direction=FFTDirection.FORWARD, flags=FFTFlags.ESTIMATE, precision=np.complex128,
                  device=0):
         self.nfft = int(nfft)
@@ -43,12 +46,6 @@ class FFT:
     @classmethod
     def new(cls, nfft, direction=FFTDirection.FORWARD, flags=FFTFlags.ESTIMATE, **kw):
         return cls(nfft, direction, flags, **kw)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            L.lib().sdsp_fft_destroy(h)
-            self._h = None
 
     METHODS = {0: "direct DFT", 1: "Stockham (LDS)", 2: "Bluestein", 3: "four-step"}
 

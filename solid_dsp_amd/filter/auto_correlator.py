@@ -18,9 +18,12 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib as L
+from .._handle import Handle
 
 
-class AutoCorrelator:
+class AutoCorrelator(Handle):
+    _family = "acorr"
+
     def __init__(self, window_size: int, delay: int, dtype=np.complex128, channels: int = 1, device: int = 0):
         self.dtype = np.dtype(dtype)
         if self.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)):
@@ -32,12 +35,6 @@ class AutoCorrelator:
         self._h = h
         if self.channels != 1:
             L.check(L.lib().sdsp_acorr_set_channels(self._h, self.channels))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            L.lib().sdsp_acorr_destroy(h)
-            self._h = None
 
     @property
     def window_size(self) -> int:

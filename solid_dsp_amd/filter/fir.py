@@ -16,32 +16,17 @@ import ctypes as C
 
 import numpy as np
 
+from .. import _handle as H
 from .. import _lib as L
 
 
-def _coef_array(coefs, coef_dtype):
-    a = np.asarray(coefs)
-    if coef_dtype is None:
-        coef_dtype = a.dtype if a.dtype in (np.float32, np.float64, np.complex64, np.complex128) else np.float64
-    return np.ascontiguousarray(a, dtype=coef_dtype)
-
-
-def _default_sample(coef_dtype):
-    return {np.dtype(np.float32): np.complex64, np.dtype(np.float64): np.complex128,
-            np.dtype(np.complex64): np.complex64, np.dtype(np.complex128): np.complex128}[np.dtype(coef_dtype)]
-
-
-class _FirBase:
+class _FirBase(H.FirHandle):
+    _family = "fir"
     _decim = False
 
     def __init__(self, coefs, scale, decimation=1, sample_dtype=None, coef_dtype=None, device=0, channels=1,
                  algo=None, host_step=None):
-        c = _coef_array(coefs, coef_dtype)
-        if sample_dtype is None:
-            sample_dtype = _default_sample(c.dtype)
-        self.dtype = L.dtype_code(c.dtype, sample_dtype)
-        self.coef_dtype = L.COEF_DTYPE[self.dtype]
-        self.sample_dtype = L.SAMPLE_DTYPE[self.dtype]
+        c = self._coefs(coefs, sample_dtype, coef_dtype)
         s = np.array([scale], dtype=self.coef_dtype)
         h = C.c_void_p()
         lib = L.lib()
@@ -49,44 +34,12 @@ class _FirBase:
             L.check(lib.sdsp_decim_create(C.byref(h), self.dtype, L.ptr(c), len(c), L.ptr(s), decimation, device))
         else:
             L.check(lib.sdsp_fir_create(C.byref(h), self.dtype, L.ptr(c), len(c), L.ptr(s), device))
-        self._h = h
-        self.device = device
-        self.channels = 1
-        if channels != 1:
-            self.set_channels(channels)
-        if algo is not None:  # default: the handle's ALGO_EXACT (bit-identical to the reference)
-            self.set_algo(algo)
+        self._adopt(h, device, channels, algo)  # algo None: the process default, ALGO_EXACT unless changed
         if host_step is not None:  # default: the handle's host step (sdsp.h SDSP_TUNE_HOST_STEP)
             self.set_host_step(host_step)
 
-    @classmethod
-    def _wrap(cls, handle, dtype, channels, device=0):
-        obj = cls.__new__(cls)
-        obj._h = handle
-        obj.dtype = dtype
-        obj.coef_dtype = L.COEF_DTYPE[dtype]
-        obj.sample_dtype = L.SAMPLE_DTYPE[dtype]
-        obj.channels = channels
-        obj.device = device
-        return obj
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            L.lib().sdsp_fir_destroy(h)
-            self._h = None
-
     # ---- configuration -------------------------------------------------
-    def set_channels(self, channels: int):
-        L.check(L.lib().sdsp_fir_set_channels(self._h, channels))
-        self.channels = channels
-
-    def set_algo(self, algo: int):
-        L.check(L.lib().sdsp_fir_set_algo(self._h, algo))
-
-    def set_tuning(self, key: int, value: int):
-        """kernel-variant knobs (SDSP_TUNE_*, include/sdsp.h): performance only"""
-        L.check(L.lib().sdsp_fir_set_tuning(self._h, int(key), int(value)))
+    set_channels, set_algo, set_tuning = H.set_channels, H.set_algo, H.set_tuning
 
     def ols_info(self):
         """(nfft, valid): segment transform size and outputs per segment ALGO_FFT would use on
@@ -126,16 +79,6 @@ class _FirBase:
         L.check(L.lib().sdsp_fir_coefficients(self._h, L.ptr(out)))
         return out
 
-    def clone(self):
-        h = C.c_void_p()
-        L.check(L.lib().sdsp_fir_clone(self._h, C.byref(h)))
-        return type(self)._wrap(h, self.dtype, self.channels, self.device)
-
-    __copy__ = clone
-
-    def reset(self):
-        L.check(L.lib().sdsp_fir_reset(self._h))
-
     def get_state(self):
         n = int(L.lib().sdsp_fir_state_len(self._h))
         hist = np.zeros(n, dtype=self.sample_dtype)
@@ -161,13 +104,8 @@ class _FirBase:
 
     def execute_block(self, samples) -> np.ndarray:
         """Filter::execute_block over host samples (channel-major [channels, n] when channels > 1)."""
-        x = np.ascontiguousarray(samples, dtype=self.sample_dtype)
-        n = x.shape[-1] if x.ndim else 0
-        if self.channels > 1 and (x.ndim != 2 or x.shape[0] != self.channels):
-            raise ValueError("multi-channel input must be [channels, n]")
-        nout = self.output_count(n)
-        y = np.zeros((self.channels, max(nout, 0)), dtype=self.sample_dtype) if self.channels > 1 else \
-            np.zeros(nout, dtype=self.sample_dtype)
+        x, n = self._block_in(samples)
+        y = self._block_out(self.output_count(n))
         got = C.c_size_t(0)
         L.check(L.lib().sdsp_fir_execute_block(self._h, L.ptr(x), n, L.ptr(y) if y.size else None, C.byref(got)))
         return y
@@ -180,9 +118,6 @@ class _FirBase:
         pout = L.device_ptr(d_out, self.sample_dtype, self.channels * self.output_count(n), self.device, "output")
         L.check(L.lib().sdsp_fir_execute_block_device(self._h, pin, n, pout, C.byref(got), L.stream_handle(stream)))
         return got.value
-
-    def synchronize(self):
-        L.check(L.lib().sdsp_fir_synchronize(self._h))
 
     def frequency_response(self, frequency: float) -> complex:
         out = np.zeros(2)
@@ -235,17 +170,14 @@ class DecimatingFIRFilter(_FirBase):
         L.check(L.lib().sdsp_decim_write(self._h, L.ptr(x), x.shape[-1]))
 
 
-class PolyPhaseFilterBank:
+class PolyPhaseFilterBank(H.FirHandle):
     """PolyPhaseFilterBank<Coef, In>  (src/filter/fir/pfb.rs:3-91)."""
+
+    _family = "pfb"
 
     def __init__(self, coefs, filters, scale=1.0, sample_dtype=None, coef_dtype=None, device=0, _interp=None,
                  algo=None, channels=1):
-        c = _coef_array(coefs, coef_dtype)
-        if sample_dtype is None:
-            sample_dtype = _default_sample(c.dtype)
-        self.dtype = L.dtype_code(c.dtype, sample_dtype)
-        self.coef_dtype = L.COEF_DTYPE[self.dtype]
-        self.sample_dtype = L.SAMPLE_DTYPE[self.dtype]
+        c = self._coefs(coefs, sample_dtype, coef_dtype)
         h = C.c_void_p()
         if _interp is None:
             s = np.array([scale], dtype=self.coef_dtype)
@@ -255,28 +187,14 @@ class PolyPhaseFilterBank:
         self._h = h
         self.device = device
         self.channels = channels
-        if algo is not None:
-            L.check(L.lib().sdsp_pfb_set_algo(self._h, algo))
+        if algo is not None:  # (the algorithm before the channels, unlike _adopt)
+            self._call("set_algo", algo)
         if channels != 1:
-            L.check(L.lib().sdsp_pfb_set_channels(self._h, channels))
+            self._call("set_channels", channels)
 
     @classmethod
     def new(cls, coefs, filters, scale, **kw):
         return cls(coefs, filters, scale, **kw)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            L.lib().sdsp_pfb_destroy(h)
-            self._h = None
-
-    def clone(self):
-        h = C.c_void_p()
-        L.check(L.lib().sdsp_pfb_clone(self._h, C.byref(h)))
-        obj = type(self).__new__(type(self))
-        obj.__dict__.update({k: v for k, v in self.__dict__.items() if k != "_h"})
-        obj._h = h
-        return obj
 
     def set_scale(self, scale):  # pfb.rs:56-59
         s = np.array([scale], dtype=self.coef_dtype)
@@ -306,9 +224,6 @@ class PolyPhaseFilterBank:
 
     coefficients = coefficents
 
-    def reset(self):  # pfb.rs:77-79
-        L.check(L.lib().sdsp_pfb_reset(self._h))
-
     def push(self, sample):  # pfb.rs:81-83
         x = np.array([sample], dtype=self.sample_dtype)
         L.check(L.lib().sdsp_pfb_push(self._h, L.ptr(x)))
@@ -321,11 +236,8 @@ class PolyPhaseFilterBank:
     def execute_block(self, samples) -> np.ndarray:
         """push each sample then emit all M branch outputs (out[n*M + p]); channel-major
         [channels, n] -> [channels, n*M] when channels > 1."""
-        x = np.ascontiguousarray(samples, dtype=self.sample_dtype)
-        if self.channels > 1 and (x.ndim != 2 or x.shape[0] != self.channels):
-            raise ValueError("multi-channel input must be [channels, n]")
-        n = x.shape[-1]
-        y = np.zeros((self.channels, n * self.len()) if self.channels > 1 else n * self.len(), dtype=self.sample_dtype)
+        x, n = self._block_in(samples)
+        y = self._block_out(n * self.len())
         if n:
             L.check(L.lib().sdsp_pfb_execute_block(self._h, L.ptr(x), n, L.ptr(y)))
         return y
@@ -336,9 +248,6 @@ class PolyPhaseFilterBank:
         pout = L.device_ptr(d_out, self.sample_dtype, self.channels * n * self.len(), self.device, "output")
         L.check(L.lib().sdsp_pfb_execute_block_device(self._h, pin, n, pout, L.stream_handle(stream)))
         return n * self.len()
-
-    def synchronize(self):
-        L.check(L.lib().sdsp_pfb_synchronize(self._h))
 
 
 class InterpolatingFIRFilter(PolyPhaseFilterBank):

@@ -14,6 +14,7 @@ import enum
 import numpy as np
 
 from .. import _lib as L
+from .._handle import Handle
 
 
 class IIRFilterType(enum.IntEnum):  # mod.rs:62-66
@@ -25,7 +26,9 @@ def _default_sample(coef_dtype):
     return {np.dtype(np.float32): np.float32, np.dtype(np.float64): np.float64}[np.dtype(coef_dtype)]
 
 
-class _IirBase:
+class _IirBase(Handle):
+    _family = "iir"
+
     _mode = 0
 
     def __init__(self, feed_forward, feed_back, iirtype=IIRFilterType.SecondOrder, factor=1, sample_dtype=None,
@@ -59,12 +62,6 @@ class _IirBase:
             self.set_channels(channels)
         if algo is not None:  # default: the handle's ALGO_EXACT (bit-identical to the reference)
             self.set_algo(algo)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            L.lib().sdsp_iir_destroy(h)
-            self._h = None
 
     def clone(self):
         h = C.c_void_p()

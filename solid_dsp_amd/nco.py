@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from ._handle import Handle
 
 
 def constrain(theta: float) -> int:  # :175-187 (the u32 phase of an angle)
@@ -25,17 +26,13 @@ class NCOError(L.SdspError):
     """NCOError(NCOErrorCode::BandwidthOutOfRange)  (src/nco/mod.rs:7-24)."""
 
 
-class NCO:
+class NCO(Handle):
+    _family = "nco"
+
     def __init__(self, device: int = 0):
         h = C.c_void_p()
         L.check(L.lib().sdsp_nco_create(C.byref(h), int(device)))
         self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            L.lib().sdsp_nco_destroy(h)
-            self._h = None
 
     def reset(self):
         L.check(L.lib().sdsp_nco_reset(self._h))

@@ -23,8 +23,8 @@ import ctypes as C
 
 import numpy as np
 
+from . import _handle as H
 from . import _lib as L
-from .filter.fir import _coef_array, _default_sample
 
 
 def count(interpolation: int, decimation: int, phase: int, n: int):
@@ -34,54 +34,26 @@ def count(interpolation: int, decimation: int, phase: int, n: int):
     return n_out.value, nxt.value
 
 
-class Resampler:
+class Resampler(H.FirHandle):
+    _family = "resamp"
     KERNELS = {1: "staged", 2: "per_output", 3: "branch"}
 
     def __init__(self, taps, interpolation=1, decimation=1, sample_dtype=None, coef_dtype=None, device=0, channels=1,
                  algo=None):
-        c = _coef_array(taps, coef_dtype)
-        if sample_dtype is None:
-            sample_dtype = _default_sample(c.dtype)
-        self.dtype = L.dtype_code(c.dtype, sample_dtype)
-        self.coef_dtype = L.COEF_DTYPE[self.dtype]
-        self.sample_dtype = L.SAMPLE_DTYPE[self.dtype]
+        c = self._coefs(taps, sample_dtype, coef_dtype)
         h = C.c_void_p()
         L.check(L.lib().sdsp_resamp_create(C.byref(h), self.dtype, L.ptr(c), len(c), int(interpolation),
                                            int(decimation), int(device)))
-        self._h = h
-        self.device = device
-        self.channels = 1
-        if channels != 1:
-            self.set_channels(channels)
-        if algo is not None:  # default: ALGO_FMA when the process default is, else ALGO_EXACT
-            self.set_algo(algo)
+        self._adopt(h, device, channels, algo)  # algo None: ALGO_FMA when the process default is, else ALGO_EXACT
 
     @classmethod
     def new(cls, taps, interpolation, decimation, **kw):
         return cls(taps, interpolation, decimation, **kw)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            L.lib().sdsp_resamp_destroy(h)
-            self._h = None
-
     # ---- configuration -------------------------------------------------
-    def set_channels(self, channels: int):
-        """zeroes the windows and the phase"""
-        L.check(L.lib().sdsp_resamp_set_channels(self._h, channels))
-        self.channels = channels
-
-    def set_algo(self, algo: int):
-        """ALGO_EXACT or ALGO_FMA"""
-        L.check(L.lib().sdsp_resamp_set_algo(self._h, int(algo)))
-
-    def get_algo(self) -> int:
-        return int(L.lib().sdsp_resamp_get_algo(self._h))
-
-    def set_tuning(self, key: int, value: int):
-        """TUNE_RESAMP_KERNEL: 0 automatic, 1 staged, 2 per output, 3 branch-stationary"""
-        L.check(L.lib().sdsp_resamp_set_tuning(self._h, int(key), int(value)))
+    set_channels = H.set_channels  # zeroes the windows and the phase
+    set_algo, get_algo = H.set_algo, H.get_algo  # ALGO_EXACT or ALGO_FMA
+    set_tuning = H.set_tuning  # TUNE_RESAMP_KERNEL: 0 automatic, 1 staged, 2 per output, 3 branch-stationary
 
     def interpolation(self) -> int:
         return int(L.lib().sdsp_resamp_interpolation(self._h))
@@ -111,29 +83,13 @@ class Resampler:
         L.check(L.lib().sdsp_resamp_info(self._h, C.byref(k), C.byref(t)))
         return k.value, t.value
 
-    def clone(self):
-        h = C.c_void_p()
-        L.check(L.lib().sdsp_resamp_clone(self._h, C.byref(h)))
-        obj = type(self).__new__(type(self))
-        obj.__dict__.update({k: v for k, v in self.__dict__.items() if k != "_h"})
-        obj._h = h
-        return obj
-
-    __copy__ = clone
-
-    def reset(self):
-        L.check(L.lib().sdsp_resamp_reset(self._h))
-
     # ---- blocks ----------------------------------------------------------
     def execute_block(self, samples) -> np.ndarray:
         """Host samples (channel-major [channels, n] when channels > 1) -> [n_out] or
         [channels, n_out]."""
-        x = np.ascontiguousarray(samples, dtype=self.sample_dtype)
-        if self.channels > 1 and (x.ndim != 2 or x.shape[0] != self.channels):
-            raise ValueError("multi-channel input must be [channels, n]")
-        n = x.shape[-1] if x.ndim else 0
+        x, n = self._block_in(samples)
         no = self.output_count(n)
-        y = np.zeros((self.channels, no) if self.channels > 1 else no, dtype=self.sample_dtype)
+        y = self._block_out(no)
         if n:
             got = C.c_size_t()
             L.check(L.lib().sdsp_resamp_execute_block(self._h, L.ptr(x), n, L.ptr(y), C.byref(got)))
@@ -151,6 +107,3 @@ class Resampler:
         L.check(L.lib().sdsp_resamp_execute_block_device(self._h, pin, n, pout, C.byref(got),
                                                          L.stream_handle(stream)))
         return got.value
-
-    def synchronize(self):
-        L.check(L.lib().sdsp_resamp_synchronize(self._h))

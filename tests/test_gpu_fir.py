@@ -307,6 +307,22 @@ def test_fir_state_clone_reset():
     assert bits_equal(hist, x[-30:])
     f.reset()
     assert bits_equal(f.execute_block(x[:50]), O.fir(O.RC64, h, 1.0).execute_block(x[:50]))
+    # clone of a decimating handle, 3 channels, at a non-zero phase (7 inputs, M = 3: phase 1)
+    h9 = rand(rng, 9, F64)
+    x3 = rand(rng, 3 * 18, C128).reshape(3, 18)
+    d = DecimatingFIRFilter(h9, 0.5, 3, sample_dtype=C128, channels=3, algo=sd.ALGO_EXACT)
+    d.execute_block(x3[:, :7])
+    c = d.clone()
+    hist, ph = c.get_state()
+    assert ph == 1 and d.get_state()[1] == 1
+    assert bits_equal(hist.reshape(3, 8)[:, 1:], x3[:, :7]) and not hist.reshape(3, 8)[:, 0].any()
+    yc = c.execute_block(x3[:, 7:])
+    assert yc.shape == (3, 4)
+    assert bits_equal(d.execute_block(x3[:, 7:]), yc)
+    for ch in range(3):
+        o = O.decim(O.RC64, h9, 0.5, 3)
+        o.execute_block(x3[ch, :7])
+        assert bits_equal(yc[ch], o.execute_block(x3[ch, 7:]))
 
 
 def test_fir_multichannel_device_matches_single():
@@ -485,6 +501,18 @@ def test_pfb_reset():
     p.execute_block(x)
     p.reset()
     assert bits_equal(p.execute_block(x), O.pfb(O.RC64, h, 4, 1.0).execute_block(x))
+    # clone of a plain filterbank, 3 channels, mid-stream: the window, scale and channels travel
+    x3 = rand(rng, 3 * 18, C128).reshape(3, 18)
+    p = PolyPhaseFilterBank(h, 4, 2.0, sample_dtype=C128, channels=3)
+    p.execute_block(x3[:, :7])
+    c = p.clone()
+    assert c.channels == 3 and c.get_scale() == p.get_scale()
+    yc = c.execute_block(x3[:, 7:])
+    assert bits_equal(p.execute_block(x3[:, 7:]), yc)
+    for ch in range(3):
+        o = O.pfb(O.RC64, h, 4, 2.0)
+        o.execute_block(x3[ch, :7])
+        assert bits_equal(yc[ch], o.execute_block(x3[ch, 7:]))
 
 
 # ---------------------------------------------------------------- synthetic stream

@@ -135,7 +135,16 @@ def test_nco_mix_c32_tolerance_and_pll():
     g.pll_step(0.3)
     o.pll_step(0.3)
     assert g.state() == o.state()
+    for _ in range(3):  # NCO::step, one register add each
+        g.step()
+        o.step()
+    assert g.state() == o.state() and g.sincos() == o.sincos()
     assert g.get_frequency() == 0.0 and g.get_phase() == 0.0  # integer-division quirk (nco/mod.rs:69-91)
+    g.set_state(0xFFFFFFF0, 0x20)
+    g.step()
+    assert g.state() == (0x10, 0x20)  # the u32 add wraps
+    g.reset()
+    assert g.state() == (0, 0)
 
 
 # ---------------------------------------------------------------- AGC
