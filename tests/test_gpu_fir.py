@@ -114,14 +114,77 @@ def test_fir_exact_bit_parity(dt, cdt, sdt, L):
         assert bits_equal(y, yo), (L, a, b)
 
 
-@pytest.mark.parametrize("dt,cdt,sdt", [DTYPES[1], DTYPES[2], DTYPES[4]])
+FMA_LS = [1, 5, 255, 256, 257, 777]  # either side of the 256-tap LDS chunk; partial last tap groups for R = 4 and 8
+# the ragged cuts of test_fir_exact_bit_parity, then a call of more than two tiles of the widest
+# type (2 * 256 * 8 outputs)
+FMA_CUTS = [0, 1, 1, 37, 37, 2048, 4999, 5000, 9500]
+
+
+def _fma_inputs(dt, cdt, sdt, L, n):
+    rng = np.random.default_rng(L * 7 + dt)
+    h = rand(rng, L, cdt)
+    scale = cdt(0.75) if np.dtype(cdt).kind == "f" else cdt(0.75 - 0.25j)
+    return h, scale, rand(rng, n, sdt)
+
+
+def _fma_refs(dt, cdt, sdt, h, scale, x, what):
+    """the f64 restatement, after asserting that the reference-order loop at the handle's own
+    precision meets the tolerance on these inputs (so a fused kernel that misses it is wrong, not
+    unlucky: on the CPU it reaches at most 5.1e-7 rel-RMS, at L = 777 with complex taps, and at most
+    0.10 of the max bound, at L = 1)"""
+    wc = C128 if np.dtype(cdt).kind == "c" else F64
+    ws = C128 if np.dtype(sdt).kind == "c" else F64
+    tol = 1e-6 if dt <= O.CC32 else 1e-13
+    ref = O.fir(_wide(dt), h.astype(wc), wc(scale)).execute_block(x.astype(ws))
+    own = O.fir(dt, h, scale).execute_block(x)
+    print(f"{what}: reference order at own precision rel-RMS {rel_rms(own, ref):.3e}")
+    assert_fir_tol(own, ref, h * scale, x, tol)
+    return ref, tol
+
+
+@pytest.mark.parametrize("dt,cdt,sdt", DTYPES)
 def test_fir_fma_tolerance(dt, cdt, sdt):
+    """fir_direct_kernel<..., false> on every type pair, L on either side of the 256-tap LDS chunk
+    and with partial last tap groups, streamed over ragged calls (empty, one sample, a call of more
+    than two tiles): both section-8d criteria against the f64 restatement, 1e-6 for 32-bit samples
+    and 1e-13 for 64-bit (an f64 kernel that computed in f32 would miss it by six orders).
+    Measured on MI355X (profiles/r16/LAB.md P3): at most 7.0e-7 (CC32, L = 777), 1.6e-15 (CC64)"""
     rng = np.random.default_rng(11)
     h = rand(rng, 256, cdt)
     x = rand(rng, 20000, sdt)
     y = FIRFilter(h, 1.0, sample_dtype=sdt, algo=sd.ALGO_FMA).execute_block(x)
     ref = O.fir(O.CC64, h.astype(C128), 1.0 + 0j).execute_block(x.astype(C128))
-    assert rel_rms(y, ref) <= 1e-6
+    assert_fir_tol(y, ref, h, x, 1e-6 if dt <= O.CC32 else 1e-13)
+    for L in FMA_LS:
+        h, scale, x = _fma_inputs(dt, cdt, sdt, L, FMA_CUTS[-1])
+        ref, tol = _fma_refs(dt, cdt, sdt, h, scale, x, f"dtype {dt} L={L}")
+        f = FIRFilter(h, scale, sample_dtype=sdt, algo=sd.ALGO_FMA)
+        y = np.concatenate([f.execute_block(x[a:b]) for a, b in zip(FMA_CUTS[:-1], FMA_CUTS[1:])])
+        print(f"dtype {dt} L={L}: fused kernel rel-RMS {rel_rms(y, ref):.3e}")
+        assert_fir_tol(y, ref, h * scale, x, tol)
+        if L > 1:
+            assert bits_equal(f.get_state()[0], x[-(L - 1):])
+
+
+@pytest.mark.parametrize("dt,cdt,sdt", DTYPES)
+def test_fir_fma_three_channels_device(dt, cdt, sdt):
+    """three channels on device buffers, two calls (the second reads each channel's own history),
+    L = 257 (a second LDS chunk of one tap), every channel under both criteria"""
+    import torch
+    L, ch, n1, n2 = 257, 3, 4099, 2500
+    h, scale, x = _fma_inputs(dt, cdt, sdt, L, ch * (n1 + n2))
+    x = x.reshape(ch, n1 + n2)
+    f = FIRFilter(h, scale, sample_dtype=sdt, channels=ch, algo=sd.ALGO_FMA)
+    ys = []
+    for a, b in ((0, n1), (n1, n1 + n2)):
+        d_in = to_dev(x[:, a:b].reshape(-1))
+        d_out = empty_dev(ch * (b - a), sdt)
+        assert f.execute_block_device(d_in, b - a, d_out, torch.cuda.current_stream()) == b - a
+        ys.append(to_host(d_out).reshape(ch, b - a))
+    y = np.concatenate(ys, axis=1)
+    for c in range(ch):
+        ref, tol = _fma_refs(dt, cdt, sdt, h, scale, x[c], f"dtype {dt} channel {c}")
+        assert_fir_tol(y[c], ref, h * scale, x[c], tol)
 
 
 def _f32_taps(L, fc):
