@@ -195,9 +195,14 @@ typedef enum {
                                       power of two >= 4 (len - 1) and >= 2^14.  Other handles accept 0 only */
     SDSP_TUNE_OLS_LONG_SEGS = 23,  /* the same path: segments per round of its three passes, 1..4096;
                                       0 (default) = what 256 MiB of scratch hold */
-    SDSP_TUNE_RESAMP_KERNEL = 24   /* rational resampler: 0 (default) automatic, 1 staged kernel, 2 one lane
+    SDSP_TUNE_RESAMP_KERNEL = 24,  /* rational resampler: 0 (default) automatic, 1 staged kernel, 2 one lane
                                       per output, 3 branch-stationary lanes; a value whose kernel does not
                                       apply to the handle's shape runs the automatic choice (sdsp_resamp_info) */
+    SDSP_TUNE_ICHAN_KERNEL = 25,   /* synthesis channeliser: 0 (default) automatic, 1 per-frame kernel, 2 ring
+                                      kernel (transformed frames kept in LDS); a value whose kernel does not
+                                      fit the handle's shape runs the automatic choice (sdsp_ichan_info) */
+    SDSP_TUNE_ICHAN_FRAMES_PER_BLOCK = 26 /* synthesis channeliser, ring kernel: frames per workgroup, any
+                                      value >= 1 (below K-1 too); 0 (default) = automatic */
 } sdsp_tune_key;
 SDSP_API int sdsp_fir_set_tuning(sdsp_fir* h, int key, int value);
 SDSP_API void sdsp_fir_destroy(sdsp_fir* h);        /* Drop */
@@ -386,6 +391,52 @@ SDSP_API int sdsp_chan_execute_block(sdsp_chan* h, const void* in, size_t n, voi
 SDSP_API int sdsp_chan_execute_block_device(sdsp_chan* h, const void* d_in, size_t n, void* d_out,
                                             size_t* frames, void* stream);
 SDSP_API int sdsp_chan_synchronize(sdsp_chan* h);
+
+/* ------------------------------------------------------------------------
+ * Synthesis ("inverse") channeliser: the counterpart of sdsp_chan, M baseband
+ * channels back into one wideband stream (build-defined; the inverse FFT fused
+ * into the polyphase bank).  Taps g are real, len >= M, K = len / M (later taps
+ * are ignored, as in sdsp_chan_create); cb[r][i] = g[r + (K-1-i) M] is the
+ * analysis channeliser's own branch table.  M a power of two, 4..4096; dtype
+ * SDSP_RC32 or SDSP_RC64.  Per stream the input is whole frames X[m][0..M) in the
+ * layout sdsp_chan_execute_block writes, [streams][frames][M] (n = frames * M
+ * samples per stream), the output n time samples, [streams][n]:
+ *
+ *     u[m]       = REVERSE_FFT_M(X[m])                 (e^{+j 2 pi k q / M}, unnormalised)
+ *     y[m M + r] = sum_{i<K} cb[r][i] * u[m-i][M-1-r]  r = 0 .. M-1
+ *
+ * Frames before the handle's first are zero.  Fed by an sdsp_chan built from
+ * taps h (branch depth K_h), a handle built from g (depth K_g) gives, in exact
+ * arithmetic,
+ *
+ *     y[m M + r] = M sum_{i<K_g} sum_{j<K_h} g[r + (K_g-1-i) M] h[(M-1-r) + (K_h-1-j) M] x[(m-i-j) M + r]
+ *
+ * (K = 1 and all-ones taps on both sides: y = M x).  One definition of the
+ * arithmetic: the transform is the one sdsp_fft REVERSE runs up to 4096 points,
+ * the branch sum starts from zero and runs i = 0 .. K-1, each step acc + c * v
+ * with a rounded multiply and a rounded add; every kernel gives the same bits.
+ * State: the last K-1 input frames per stream, zero after create, reset and
+ * set_streams.  Blocks as sdsp_chan_execute_block[_device]: n a multiple of M,
+ * n = 0 a no-op, no overlap of input and output.
+ * ------------------------------------------------------------------------ */
+typedef struct sdsp_ichan sdsp_ichan;
+SDSP_API int sdsp_ichan_create(sdsp_ichan** out, int dtype, const void* taps, size_t len, size_t channels,
+                               int device);
+SDSP_API void sdsp_ichan_destroy(sdsp_ichan* h);
+SDSP_API int sdsp_ichan_set_streams(sdsp_ichan* h, size_t streams);
+/* kernel-variant knobs: SDSP_TUNE_ICHAN_KERNEL, SDSP_TUNE_ICHAN_FRAMES_PER_BLOCK (performance only) */
+SDSP_API int sdsp_ichan_set_tuning(sdsp_ichan* h, int key, int value);
+SDSP_API int sdsp_ichan_reset(sdsp_ichan* h);
+SDSP_API size_t sdsp_ichan_channels(const sdsp_ichan* h);      /* M */
+SDSP_API size_t sdsp_ichan_subfilter_len(const sdsp_ichan* h); /* K */
+SDSP_API int sdsp_ichan_execute_block(sdsp_ichan* h, const void* in, size_t n, void* out, size_t* frames);
+SDSP_API int sdsp_ichan_execute_block_device(sdsp_ichan* h, const void* d_in, size_t n, void* d_out,
+                                             size_t* frames, void* stream);
+/* what the next call runs: *kernel = 1 per-frame, 2 ring; *frames_per_block = the ring kernel's frames
+ * per workgroup on a long block (an automatic value shrinks on blocks too short to fill the device
+ * at it), 1 on the per-frame kernel.  Either pointer may be null */
+SDSP_API int sdsp_ichan_info(const sdsp_ichan* h, int* kernel, size_t* frames_per_block);
+SDSP_API int sdsp_ichan_synchronize(sdsp_ichan* h);
 
 /* ------------------------------------------------------------------------
  * DotProduct (src/dot_product/mod.rs:37-171): DotProduct::new(&coefs, direction)

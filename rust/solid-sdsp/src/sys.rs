@@ -8,6 +8,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct sdsp_iir { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_fft { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_chan { _p: [u8; 0] }
+#[repr(C)] pub struct sdsp_ichan { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_acorr { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_nco { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_agc { _p: [u8; 0] }
@@ -154,6 +155,21 @@ extern "C" {
     pub fn sdsp_chan_destroy(h: *mut sdsp_chan);
     pub fn sdsp_chan_execute_block(h: *mut sdsp_chan, input: *const c_void, n: usize, out: *mut c_void,
                                    frames: *mut usize) -> c_int;
+    // synthesis channeliser (build-defined: the inverse FFT fused into the polyphase bank)
+    pub fn sdsp_ichan_create(out: *mut *mut sdsp_ichan, dtype: c_int, taps: *const c_void, len: usize,
+                             channels: usize, device: c_int) -> c_int;
+    pub fn sdsp_ichan_destroy(h: *mut sdsp_ichan);
+    pub fn sdsp_ichan_set_streams(h: *mut sdsp_ichan, streams: usize) -> c_int;
+    pub fn sdsp_ichan_set_tuning(h: *mut sdsp_ichan, key: c_int, value: c_int) -> c_int;
+    pub fn sdsp_ichan_reset(h: *mut sdsp_ichan) -> c_int;
+    pub fn sdsp_ichan_channels(h: *const sdsp_ichan) -> usize;
+    pub fn sdsp_ichan_subfilter_len(h: *const sdsp_ichan) -> usize;
+    pub fn sdsp_ichan_execute_block(h: *mut sdsp_ichan, input: *const c_void, n: usize, out: *mut c_void,
+                                    frames: *mut usize) -> c_int;
+    pub fn sdsp_ichan_execute_block_device(h: *mut sdsp_ichan, d_in: *const c_void, n: usize, d_out: *mut c_void,
+                                           frames: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn sdsp_ichan_info(h: *const sdsp_ichan, kernel: *mut c_int, frames_per_block: *mut usize) -> c_int;
+    pub fn sdsp_ichan_synchronize(h: *mut sdsp_ichan) -> c_int;
 
     // tap / loop-filter design (firdes/mod.rs:243-368, iirdes/pll/mod.rs:24-99)
     pub fn sdsp_kaiser_beta(stop_band_attenuation: f64) -> f64;

@@ -12,6 +12,8 @@ from . import filter, group_delay, fft, dot_product, channelizer  # noqa: F401
 from .fft import FFT, FFTDirection, FFTFlags  # noqa: F401
 from .dot_product import DotProduct, Direction  # noqa: F401
 from .channelizer import Channelizer  # noqa: F401
+from . import synthesizer  # noqa: F401
+from .synthesizer import ChannelSynthesizer  # noqa: F401
 from . import nco  # noqa: F401
 from .nco import NCO, NCOError  # noqa: F401
 from . import auto_gain_control  # noqa: F401

@@ -26,6 +26,7 @@ TUNE_HOST_STEP, TUNE_HOST_BLOCK_MACS = 16, 17
 TUNE_FFT_GROUP, TUNE_FFT_WAVE1024, TUNE_ACORR_KERNEL, TUNE_AGC_KERNEL = 18, 19, 20, 21
 TUNE_OLS_LONG_LOG2N, TUNE_OLS_LONG_SEGS = 22, 23
 TUNE_RESAMP_KERNEL = 24
+TUNE_ICHAN_KERNEL, TUNE_ICHAN_FRAMES_PER_BLOCK = 25, 26
 
 _PAIRS = {
     (np.dtype(np.float32), np.dtype(np.float32)): RR32,
@@ -193,6 +194,18 @@ def _declare(L):
         "sdsp_resamp_info": (i, [vp, C.POINTER(i), szp]),
         "sdsp_resamp_synchronize": (i, [vp]),
         "sdsp_resamp_count": (i, [sz, sz, sz, sz, szp, szp]),
+        # synthesis channeliser (inverse FFT fused into the polyphase bank)
+        "sdsp_ichan_create": (i, [vpp, i, vp, sz, sz, i]),
+        "sdsp_ichan_destroy": (None, [vp]),
+        "sdsp_ichan_set_streams": (i, [vp, sz]),
+        "sdsp_ichan_set_tuning": (i, [vp, i, i]),
+        "sdsp_ichan_reset": (i, [vp]),
+        "sdsp_ichan_channels": (sz, [vp]),
+        "sdsp_ichan_subfilter_len": (sz, [vp]),
+        "sdsp_ichan_execute_block": (i, [vp, vp, sz, vp, szp]),
+        "sdsp_ichan_execute_block_device": (i, [vp, vp, sz, vp, szp, vp]),
+        "sdsp_ichan_info": (i, [vp, C.POINTER(i), szp]),
+        "sdsp_ichan_synchronize": (i, [vp]),
         "sdsp_synth_f32_device": (i, [vp, C.c_uint64, C.c_uint64, C.c_uint64, sz, vp]),
         "sdsp_bandwidth_copy_device": (i, [vp, vp, sz, vp]),
         "sdsp_firdes_kaiser": (i, [sz, d, d, d, dp]),

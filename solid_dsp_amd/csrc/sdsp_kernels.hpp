@@ -198,6 +198,27 @@ hipError_t launch_chan(bool f64, const ChanArgs& a, hipStream_t s);
 // streaming M = 1024 kernel (kern_chan1024.hip); false = not applicable
 bool try_launch_chan1024(const ChanArgs& a, hipStream_t s, hipError_t* err);
 
+// synthesis channeliser (kern_ichan.hip): frames of M channel samples in, n = frames * M time samples out
+constexpr int kIchanPerFrame = 1;  // one workgroup per (frame, stream), K transforms per frame
+constexpr int kIchanRing = 2;      // one workgroup per (chunk of frames, stream), transformed frames kept in LDS
+struct IchanArgs {
+    const void* x;     // [streams][frames][M]
+    const void* hist;  // [streams][(K-1) M] untransformed input frames, oldest first
+    const void* cbt;   // [K][M] real branch coefficients, cbt[i][r] = g[r + (K-1-i) M]
+    void* y;           // [streams][n]
+    const void* tw;
+    int M, logM, K;
+    size_t n, frames, streams;
+    int kernel;            // SDSP_TUNE_ICHAN_KERNEL: 0 automatic, or a kIchan* value
+    int frames_per_block;  // SDSP_TUNE_ICHAN_FRAMES_PER_BLOCK: ring kernel, 0 automatic
+};
+struct IchanPlan {
+    int kernel;               // kIchanPerFrame / kIchanRing
+    size_t frames_per_block;  // frames per workgroup on a long block (1 on the per-frame kernel)
+};
+IchanPlan ichan_plan(bool f64, int M, int K, int kernel, int frames_per_block);
+hipError_t launch_ichan(bool f64, const IchanArgs& a, hipStream_t s);
+
 // batched DotProduct::execute
 struct DotArgs {
     const void* coefs;
