@@ -201,8 +201,14 @@ typedef enum {
     SDSP_TUNE_ICHAN_KERNEL = 25,   /* synthesis channeliser: 0 (default) automatic, 1 per-frame kernel, 2 ring
                                       kernel (transformed frames kept in LDS); a value whose kernel does not
                                       fit the handle's shape runs the automatic choice (sdsp_ichan_info) */
-    SDSP_TUNE_ICHAN_FRAMES_PER_BLOCK = 26 /* synthesis channeliser, ring kernel: frames per workgroup, any
+    SDSP_TUNE_ICHAN_FRAMES_PER_BLOCK = 26, /* synthesis channeliser, ring kernel: frames per workgroup, any
                                       value >= 1 (below K-1 too); 0 (default) = automatic */
+    SDSP_TUNE_OSCHAN_KERNEL = 27,  /* oversampled channeliser: 0 (default) automatic, 1 per-frame kernel, 2
+                                      sliding kernel (the stream's window kept in LDS); a value whose kernel
+                                      does not fit the handle's shape runs the automatic choice
+                                      (sdsp_oschan_info) */
+    SDSP_TUNE_OSCHAN_FRAMES_PER_BLOCK = 28 /* oversampled channeliser, sliding kernel: frames per workgroup,
+                                      any value >= 1; 0 (default) = automatic */
 } sdsp_tune_key;
 SDSP_API int sdsp_fir_set_tuning(sdsp_fir* h, int key, int value);
 SDSP_API void sdsp_fir_destroy(sdsp_fir* h);        /* Drop */
@@ -437,6 +443,59 @@ SDSP_API int sdsp_ichan_execute_block_device(sdsp_ichan* h, const void* d_in, si
  * at it), 1 on the per-frame kernel.  Either pointer may be null */
 SDSP_API int sdsp_ichan_info(const sdsp_ichan* h, int* kernel, size_t* frames_per_block);
 SDSP_API int sdsp_ichan_synchronize(sdsp_ichan* h);
+
+/* ------------------------------------------------------------------------
+ * Oversampled analysis channeliser: M channels, one frame every D <= M samples
+ * (build-defined; sdsp_chan is the critically sampled case D = M).  Taps h are
+ * real, len >= M, K = len / M (later taps are ignored, as in sdsp_chan_create);
+ * cb[p][i] = h[p + (K-1-i) M] is the channeliser's own branch table.  M a power
+ * of two, 4..4096; 1 <= decimation D <= M; dtype SDSP_RC32 or SDSP_RC64.  Per
+ * stream, with x[<0] = 0 and m the frame index since create / reset /
+ * set_streams (64-bit, carried across calls):
+ *
+ *     v_p[m] = sum_{i<K} cb[p][i] * x[(m+1) D - 1 - p - i M]      p = 0 .. M-1
+ *     w_q[m] = v_{(q + (m+1) D) mod M}[m]                  (an index rotation, no arithmetic)
+ *     Y[m]   = FORWARD_FFT_M(w[m])                         (unnormalised)
+ *
+ * - D = M is sdsp_chan: the rotation is 0 and the index is (m-i) M + (M-1-p).
+ * - Every channel is a plain down-converter: with g[p + i M] = h[p + (K-1-i) M],
+ *       Y[m][k] = (g * (x[n] e^{+j 2 pi k (n+1) / M}))[(m+1) D - 1],
+ *   a mix, a filter and a decimation by D with a phase-continuous oscillator.
+ *   The rotation buys this: without it the output is a sliding STFT whose
+ *   channel k turns by e^{-j 2 pi k (m+1) D / M} from frame to frame.
+ * - It is an index rotation, not a multiply by a twiddle (which would change
+ *   the bits and cost a rounding).
+ *
+ * One definition of the arithmetic: the branch sum starts from zero and runs
+ * i = 0 .. K-1, each step acc + c * v with a rounded multiply and a rounded add;
+ * the transform is the one sdsp_fft FORWARD runs up to 4096 points; every
+ * kernel, at every frames-per-workgroup value and every call split, gives the
+ * same bits.  Blocks: n (per stream) a multiple of D gives frames = n / D
+ * frames, out[s][frame][M] (n M / D samples per stream); n = 0 is a no-op;
+ * input and output may not overlap.  State: the last K M - D input samples per
+ * stream and the frame counter (sdsp_oschan_phase); both zero after create,
+ * reset and set_streams; a refused call changes neither.
+ * ------------------------------------------------------------------------ */
+typedef struct sdsp_oschan sdsp_oschan;
+SDSP_API int sdsp_oschan_create(sdsp_oschan** out, int dtype, const void* taps, size_t len, size_t channels,
+                                size_t decimation, int device);
+SDSP_API void sdsp_oschan_destroy(sdsp_oschan* h);
+SDSP_API int sdsp_oschan_set_streams(sdsp_oschan* h, size_t streams);
+/* kernel-variant knobs: SDSP_TUNE_OSCHAN_KERNEL, SDSP_TUNE_OSCHAN_FRAMES_PER_BLOCK (performance only) */
+SDSP_API int sdsp_oschan_set_tuning(sdsp_oschan* h, int key, int value);
+SDSP_API int sdsp_oschan_reset(sdsp_oschan* h);
+SDSP_API size_t sdsp_oschan_channels(const sdsp_oschan* h);      /* M */
+SDSP_API size_t sdsp_oschan_decimation(const sdsp_oschan* h);    /* D */
+SDSP_API size_t sdsp_oschan_subfilter_len(const sdsp_oschan* h); /* K */
+SDSP_API size_t sdsp_oschan_phase(const sdsp_oschan* h);         /* (frames so far * D) mod M; 0 for a null handle */
+SDSP_API int sdsp_oschan_execute_block(sdsp_oschan* h, const void* in, size_t n, void* out, size_t* frames);
+SDSP_API int sdsp_oschan_execute_block_device(sdsp_oschan* h, const void* d_in, size_t n, void* d_out,
+                                              size_t* frames, void* stream);
+/* what the next call runs: *kernel = 1 per-frame, 2 sliding; *frames_per_block = the sliding kernel's
+ * frames per workgroup on a long block (an automatic value shrinks on blocks too short to fill the
+ * device at it), 1 on the per-frame kernel.  Either pointer may be null */
+SDSP_API int sdsp_oschan_info(const sdsp_oschan* h, int* kernel, size_t* frames_per_block);
+SDSP_API int sdsp_oschan_synchronize(sdsp_oschan* h);
 
 /* ------------------------------------------------------------------------
  * DotProduct (src/dot_product/mod.rs:37-171): DotProduct::new(&coefs, direction)

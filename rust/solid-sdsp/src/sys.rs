@@ -9,6 +9,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct sdsp_fft { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_chan { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_ichan { _p: [u8; 0] }
+#[repr(C)] pub struct sdsp_oschan { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_acorr { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_nco { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_agc { _p: [u8; 0] }
@@ -170,6 +171,22 @@ extern "C" {
                                            frames: *mut usize, stream: *mut c_void) -> c_int;
     pub fn sdsp_ichan_info(h: *const sdsp_ichan, kernel: *mut c_int, frames_per_block: *mut usize) -> c_int;
     pub fn sdsp_ichan_synchronize(h: *mut sdsp_ichan) -> c_int;
+    pub fn sdsp_oschan_create(out: *mut *mut sdsp_oschan, dtype: c_int, taps: *const c_void, len: usize,
+                              channels: usize, decimation: usize, device: c_int) -> c_int;
+    pub fn sdsp_oschan_destroy(h: *mut sdsp_oschan);
+    pub fn sdsp_oschan_set_streams(h: *mut sdsp_oschan, streams: usize) -> c_int;
+    pub fn sdsp_oschan_set_tuning(h: *mut sdsp_oschan, key: c_int, value: c_int) -> c_int;
+    pub fn sdsp_oschan_reset(h: *mut sdsp_oschan) -> c_int;
+    pub fn sdsp_oschan_channels(h: *const sdsp_oschan) -> usize;
+    pub fn sdsp_oschan_decimation(h: *const sdsp_oschan) -> usize;
+    pub fn sdsp_oschan_subfilter_len(h: *const sdsp_oschan) -> usize;
+    pub fn sdsp_oschan_phase(h: *const sdsp_oschan) -> usize;
+    pub fn sdsp_oschan_execute_block(h: *mut sdsp_oschan, input: *const c_void, n: usize, out: *mut c_void,
+                                     frames: *mut usize) -> c_int;
+    pub fn sdsp_oschan_execute_block_device(h: *mut sdsp_oschan, d_in: *const c_void, n: usize, d_out: *mut c_void,
+                                            frames: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn sdsp_oschan_info(h: *const sdsp_oschan, kernel: *mut c_int, frames_per_block: *mut usize) -> c_int;
+    pub fn sdsp_oschan_synchronize(h: *mut sdsp_oschan) -> c_int;
 
     // tap / loop-filter design (firdes/mod.rs:243-368, iirdes/pll/mod.rs:24-99)
     pub fn sdsp_kaiser_beta(stop_band_attenuation: f64) -> f64;

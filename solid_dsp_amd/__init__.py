@@ -14,6 +14,8 @@ from .dot_product import DotProduct, Direction  # noqa: F401
 from .channelizer import Channelizer  # noqa: F401
 from . import synthesizer  # noqa: F401
 from .synthesizer import ChannelSynthesizer  # noqa: F401
+from . import oschan  # noqa: F401
+from .oschan import OversampledChannelizer  # noqa: F401
 from . import nco  # noqa: F401
 from .nco import NCO, NCOError  # noqa: F401
 from . import auto_gain_control  # noqa: F401

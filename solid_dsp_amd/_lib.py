@@ -27,6 +27,7 @@ TUNE_FFT_GROUP, TUNE_FFT_WAVE1024, TUNE_ACORR_KERNEL, TUNE_AGC_KERNEL = 18, 19, 
 TUNE_OLS_LONG_LOG2N, TUNE_OLS_LONG_SEGS = 22, 23
 TUNE_RESAMP_KERNEL = 24
 TUNE_ICHAN_KERNEL, TUNE_ICHAN_FRAMES_PER_BLOCK = 25, 26
+TUNE_OSCHAN_KERNEL, TUNE_OSCHAN_FRAMES_PER_BLOCK = 27, 28
 
 _PAIRS = {
     (np.dtype(np.float32), np.dtype(np.float32)): RR32,
@@ -206,6 +207,19 @@ def _declare(L):
         "sdsp_ichan_execute_block_device": (i, [vp, vp, sz, vp, szp, vp]),
         "sdsp_ichan_info": (i, [vp, C.POINTER(i), szp]),
         "sdsp_ichan_synchronize": (i, [vp]),
+        "sdsp_oschan_create": (i, [vpp, i, vp, sz, sz, sz, i]),
+        "sdsp_oschan_destroy": (None, [vp]),
+        "sdsp_oschan_set_streams": (i, [vp, sz]),
+        "sdsp_oschan_set_tuning": (i, [vp, i, i]),
+        "sdsp_oschan_reset": (i, [vp]),
+        "sdsp_oschan_channels": (sz, [vp]),
+        "sdsp_oschan_decimation": (sz, [vp]),
+        "sdsp_oschan_subfilter_len": (sz, [vp]),
+        "sdsp_oschan_phase": (sz, [vp]),
+        "sdsp_oschan_execute_block": (i, [vp, vp, sz, vp, szp]),
+        "sdsp_oschan_execute_block_device": (i, [vp, vp, sz, vp, szp, vp]),
+        "sdsp_oschan_info": (i, [vp, C.POINTER(i), szp]),
+        "sdsp_oschan_synchronize": (i, [vp]),
         "sdsp_synth_f32_device": (i, [vp, C.c_uint64, C.c_uint64, C.c_uint64, sz, vp]),
         "sdsp_bandwidth_copy_device": (i, [vp, vp, sz, vp]),
         "sdsp_firdes_kaiser": (i, [sz, d, d, d, dp]),

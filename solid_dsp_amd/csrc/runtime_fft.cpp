@@ -1,5 +1,6 @@
 // C-ABI runtime for FFT (src/fft/mod.rs:175-215), the PFB + FFT channeliser
-// (build-defined), its synthesis counterpart (sdsp_ichan) and batched DotProduct::execute
+// (build-defined), its synthesis counterpart (sdsp_ichan), its oversampled form
+// (sdsp_oschan) and batched DotProduct::execute
 // (src/dot_product/mod.rs:153-171).
 #include <hip/hip_runtime.h>
 
@@ -141,6 +142,16 @@ struct sdsp_ichan : HandleCore {
     PingPong hist;   // [streams][(K-1) M] input frames (untransformed), oldest first
     int kernel = 0;  // SDSP_TUNE_ICHAN_KERNEL
     int fpb = 0;     // SDSP_TUNE_ICHAN_FRAMES_PER_BLOCK
+};
+
+struct sdsp_oschan : HandleCore {
+    int dtype = SDSP_RC32;
+    size_t M = 0, K = 0, D = 0, streams = 1;
+    DevBuf cbt, tw;    // cbt[i][p] = h[p + (K-1-i) M], [K][M]
+    PingPong hist;     // [streams][K M - D] input samples, oldest first
+    size_t phase = 0;  // (frames so far * D) mod M
+    int kernel = 0;    // SDSP_TUNE_OSCHAN_KERNEL
+    int fpb = 0;       // SDSP_TUNE_OSCHAN_FRAMES_PER_BLOCK
 };
 
 extern "C" {
@@ -499,6 +510,137 @@ int sdsp_ichan_execute_block(sdsp_ichan* h, const void* in, size_t n, void* out,
 }
 
 int sdsp_ichan_synchronize(sdsp_ichan* h) {
+    if (!h) return SDSP_E_INVALID_ARGUMENT;
+    DeviceGuard g(h->device);
+    return h->quiesce();
+}
+
+// ---- oversampled analysis channeliser ----------------------------------------
+int sdsp_oschan_create(sdsp_oschan** out, int dtype, const void* taps, size_t len, size_t M, size_t D, int device) {
+    if (!out) return SDSP_E_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (dtype != SDSP_RC32 && dtype != SDSP_RC64) {
+        set_error("oversampled channeliser takes real taps and complex samples (SDSP_RC32 / SDSP_RC64)");
+        return SDSP_E_UNSUPPORTED;
+    }
+    if (!taps && len > 0) { set_error("taps pointer is null"); return SDSP_E_INVALID_ARGUMENT; }
+    if (M == 0) { set_error("FIR Filter Error NotEnoughFilters"); return SDSP_E_NOT_ENOUGH_FILTERS; }
+    if (len == 0) { set_error("FIR Filter Error CoefficientsLengthZero"); return SDSP_E_COEFFICIENTS_LENGTH_ZERO; }
+    if (!is_pow2(M) || M < 4 || M > 4096) {
+        set_error("channel count must be a power of two in [4, 4096]");
+        return SDSP_E_UNSUPPORTED;
+    }
+    if (D == 0 || D > M) {
+        set_error("decimation (the frame stride) must be in [1, channels]");
+        return SDSP_E_UNSUPPORTED;
+    }
+    const size_t K = len / M;
+    if (K == 0) { set_error("fewer taps than channels"); return SDSP_E_INVALID_ARGUMENT; }
+    int st = check_device(device, nullptr);
+    if (st) return st;
+    DeviceGuard g(device);
+    sdsp_oschan* h = new sdsp_oschan();
+    h->dtype = dtype;
+    h->M = M;
+    h->K = K;
+    h->D = D;
+    // row i of the table is the taps' block K-1-i; taps beyond K M are ignored
+    const size_t row = M * coef_bytes(dtype);
+    std::vector<unsigned char> cbt(K * row);
+    for (size_t i = 0; i < K; ++i) std::memcpy(&cbt[i * row], (const unsigned char*)taps + (K - 1 - i) * row, row);
+    hipError_t e = h->open(device);
+    if (e == hipSuccess) e = h->cbt.ensure(cbt.size());
+    if (e == hipSuccess) e = hipMemcpy(h->cbt.p, cbt.data(), cbt.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { st = device_status(e, "oschan create"); sdsp_oschan_destroy(h); return st; }
+    st = make_twiddles(h->tw, M, dtype == SDSP_RC64);
+    if (!st) st = sdsp_oschan_set_streams(h, 1);
+    if (st) { sdsp_oschan_destroy(h); return st; }
+    *out = h;
+    return SDSP_OK;
+}
+
+void sdsp_oschan_destroy(sdsp_oschan* h) { destroy_handle(h); }
+
+int sdsp_oschan_set_streams(sdsp_oschan* h, size_t streams) {
+    if (!h || streams == 0) return SDSP_E_INVALID_ARGUMENT;
+    DeviceGuard g(h->device);
+    SDSP_TRY(h->fence.wait(), "wait for queued work");  // a queued block may still read the history
+    h->streams = streams;
+    SDSP_TRY(h->hist.reset(streams * (h->K * h->M - h->D) * sample_bytes(h->dtype), h->stream), "zero history");
+    h->phase = 0;
+    return h->quiesce();
+}
+
+int sdsp_oschan_set_tuning(sdsp_oschan* h, int key, int value) {
+    if (!h) return SDSP_E_INVALID_ARGUMENT;
+    if (key == SDSP_TUNE_OSCHAN_KERNEL && value >= 0 && value <= 2) h->kernel = value;
+    else if (key == SDSP_TUNE_OSCHAN_FRAMES_PER_BLOCK && value >= 0) h->fpb = value;
+    else return SDSP_E_INVALID_ARGUMENT;
+    return SDSP_OK;
+}
+
+int sdsp_oschan_reset(sdsp_oschan* h) { return h ? sdsp_oschan_set_streams(h, h->streams) : SDSP_E_INVALID_ARGUMENT; }
+
+size_t sdsp_oschan_channels(const sdsp_oschan* h) { return h ? h->M : 0; }
+size_t sdsp_oschan_decimation(const sdsp_oschan* h) { return h ? h->D : 0; }
+size_t sdsp_oschan_subfilter_len(const sdsp_oschan* h) { return h ? h->K : 0; }
+size_t sdsp_oschan_phase(const sdsp_oschan* h) { return h ? h->phase : 0; }
+
+int sdsp_oschan_info(const sdsp_oschan* h, int* kernel, size_t* frames_per_block) {
+    if (!h) return SDSP_E_INVALID_ARGUMENT;
+    const OschanPlan p = oschan_plan(h->dtype == SDSP_RC64, (int)h->M, (int)h->K, (int)h->D, h->kernel, h->fpb);
+    if (kernel) *kernel = p.kernel;
+    if (frames_per_block) *frames_per_block = p.frames_per_block;
+    return SDSP_OK;
+}
+
+int sdsp_oschan_execute_block_device(sdsp_oschan* h, const void* d_in, size_t n, void* d_out, size_t* frames,
+                                     void* stream) {
+    if (!h) return SDSP_E_INVALID_ARGUMENT;
+    if (n % h->D) {
+        set_error("oversampled channeliser blocks must be a whole number of D-sample frame strides");
+        return SDSP_E_INVALID_ARGUMENT;
+    }
+    const size_t fr = n / h->D;
+    if (frames) *frames = fr;
+    if (fr == 0) return SDSP_OK;
+    const size_t sb = sample_bytes(h->dtype);
+    if (ranges_overlap(d_in, h->streams * n * sb, d_out, h->streams * fr * h->M * sb)) {
+        set_error("input and output blocks overlap (in-place channelising is not supported)");
+        return SDSP_E_INVALID_ARGUMENT;
+    }
+    DeviceGuard g(h->device);
+    hipStream_t s = pick(stream, h->stream);
+    SDSP_TRY(h->fence.order_before(s), "order after queued work");  // the history this launch reads
+    const OschanArgs a{d_in, h->hist.front(), h->cbt.p, d_out, h->tw.p, (int)h->M, ilog2(h->M), (int)h->K,
+                       (int)h->D, (int)h->phase, n, fr, h->streams, h->kernel, h->fpb};
+    SDSP_TRY(launch_oschan(h->dtype == SDSP_RC64, a, s), "oversampled channeliser");
+    const int H = (int)(h->K * h->M - h->D);
+    SDSP_TRY(launch_hist_update(h->dtype, d_in, h->hist.front(), h->hist.back(), n, H, h->streams, s),
+          "history update");
+    h->hist.flip();
+    h->phase = (h->phase + n) % h->M;  // n = frames * D
+    SDSP_TRY(h->fence.record(s), "record fence");
+    return SDSP_OK;
+}
+
+int sdsp_oschan_execute_block(sdsp_oschan* h, const void* in, size_t n, void* out, size_t* frames) {
+    if (!h) return SDSP_E_INVALID_ARGUMENT;
+    DeviceGuard g(h->device);
+    if (n % h->D) {
+        set_error("oversampled channeliser blocks must be a whole number of D-sample frame strides");
+        return SDSP_E_INVALID_ARGUMENT;
+    }
+    const size_t fr = n / h->D, sb = sample_bytes(h->dtype);
+    if (frames) *frames = fr;
+    if (n == 0) return SDSP_OK;
+    return h->staged(in, h->streams * n * sb, out, h->streams * fr * h->M * sb,
+                     [&](const void* d_in, void* d_out, hipStream_t s) {
+                         return sdsp_oschan_execute_block_device(h, d_in, n, d_out, nullptr, s);
+                     });
+}
+
+int sdsp_oschan_synchronize(sdsp_oschan* h) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
     DeviceGuard g(h->device);
     return h->quiesce();

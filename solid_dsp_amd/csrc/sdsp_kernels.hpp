@@ -219,6 +219,28 @@ struct IchanPlan {
 IchanPlan ichan_plan(bool f64, int M, int K, int kernel, int frames_per_block);
 hipError_t launch_ichan(bool f64, const IchanArgs& a, hipStream_t s);
 
+// oversampled analysis channeliser (kern_oschan.hip): n = frames * D time samples in, frames of M channel samples out
+constexpr int kOschanPerFrame = 1;  // one workgroup per (frame, stream), branch sums from global memory
+constexpr int kOschanSlide = 2;     // one workgroup per (chunk of frames, stream), the stream's window kept in LDS
+struct OschanArgs {
+    const void* x;     // [streams][n]
+    const void* hist;  // [streams][K M - D] input samples, oldest first
+    const void* cbt;   // [K][M] real branch coefficients, cbt[i][p] = h[p + (K-1-i) M]
+    void* y;           // [streams][frames][M]
+    const void* tw;
+    int M, logM, K, D;
+    int phase;         // (frames before this call * D) mod M
+    size_t n, frames, streams;
+    int kernel;            // SDSP_TUNE_OSCHAN_KERNEL: 0 automatic, or a kOschan* value
+    int frames_per_block;  // SDSP_TUNE_OSCHAN_FRAMES_PER_BLOCK: sliding kernel, 0 automatic
+};
+struct OschanPlan {
+    int kernel;               // kOschanPerFrame / kOschanSlide
+    size_t frames_per_block;  // frames per workgroup on a long block (1 on the per-frame kernel)
+};
+OschanPlan oschan_plan(bool f64, int M, int K, int D, int kernel, int frames_per_block);
+hipError_t launch_oschan(bool f64, const OschanArgs& a, hipStream_t s);
+
 // batched DotProduct::execute
 struct DotArgs {
     const void* coefs;
