@@ -207,8 +207,11 @@ typedef enum {
                                       sliding kernel (the stream's window kept in LDS); a value whose kernel
                                       does not fit the handle's shape runs the automatic choice
                                       (sdsp_oschan_info) */
-    SDSP_TUNE_OSCHAN_FRAMES_PER_BLOCK = 28 /* oversampled channeliser, sliding kernel: frames per workgroup,
+    SDSP_TUNE_OSCHAN_FRAMES_PER_BLOCK = 28, /* oversampled channeliser, sliding kernel: frames per workgroup,
                                       any value >= 1; 0 (default) = automatic */
+    SDSP_TUNE_ARB_KERNEL = 29      /* arbitrary-rate resampler: 0 (default) automatic, 1 staged kernel, 2 one
+                                      lane per output; a value whose kernel does not apply to the handle's
+                                      shape and step runs the automatic choice (sdsp_arb_info) */
 } sdsp_tune_key;
 SDSP_API int sdsp_fir_set_tuning(sdsp_fir* h, int key, int value);
 SDSP_API void sdsp_fir_destroy(sdsp_fir* h);        /* Drop */
@@ -753,6 +756,97 @@ SDSP_API int sdsp_resamp_synchronize(sdsp_resamp* h);
  * phase + n * interpolation does not fit 63 bits. */
 SDSP_API int sdsp_resamp_count(size_t interpolation, size_t decimation, size_t phase, size_t n, size_t* n_out,
                                size_t* next_phase);
+
+/* ------------------------------------------------------------------------
+ * Arbitrary-rate resampler: any rate from one polyphase bank.  A build-defined
+ * composition on the reference's PolyPhaseFilterBank (pfb.rs: push, then
+ * execute(index) with a caller-chosen branch): an interpolating FIR with P
+ * branches whose interpolated stream is never written; each output is a linear
+ * interpolation between two neighbouring interpolated samples, chosen by a
+ * 64-bit fixed-point time accumulator.  A handle is an interpolator handle
+ * (sdsp_interp_create with interpolation = P) plus two registers:
+ *   step  input samples per output, unsigned Q32.32, 2^16 <= step <= 2^48 (the
+ *         rate 2^32 / step lies in [2^-16, 2^16])
+ *   t     time of the next output, Q32.32, measured from the first input of
+ *         the next call; 0 after create and reset; all channels share it
+ * Let z be the EXACT interpolator's stream over the handle's whole input
+ * history, z(j * P + p) = sum_{i<K} cb[p][i] * x[j - i], with z(-1) = 0 after
+ * create and reset.  A call of n inputs per channel, n < 2^31 (a larger n fails
+ * with SDSP_E_INVALID_ARGUMENT), computes
+ *     n_out = 0 if t >= n * 2^32, else ceil((n * 2^32 - t) / step)
+ *     for k < n_out:
+ *         T = t + k * step;  j = T >> 32;  f = T & (2^32 - 1)
+ *         v = f * P (64-bit);  b = v >> 32;  m = v & (2^32 - 1)
+ *         mu = (R)m * 2^-32       R = the sample's real type; (R)m is the
+ *                                 ordinary round-to-nearest conversion
+ *         u = j * P + b
+ *         a = z(u - 1);  c = z(u)
+ *         out[k] = a + mu * (c - a)       on re and im separately; mu is real
+ *     t <- t + n_out * step - n * 2^32
+ * For b >= 1, a and c are branches b - 1 and b on the window ending at x[j];
+ * for b = 0, a is branch P - 1 on the window ending at x[j - 1] (it reaches
+ * x[j - K]: for j = 0 the oldest sample of the window).  Outputs are
+ * independent of each other: output k follows from k alone.
+ *   No look-ahead: the handle interpolates between z(u - 1) and z(u), so it
+ *     delays by 1 / P of an input sample relative to interpolating between
+ *     z(u) and z(u + 1).
+ *   dtype: any of the six pairs.  Check order of create: dtype out of range,
+ *     null taps with len > 0, step out of range (the message names "step"),
+ *     filters > 2^31 - 1 (all SDSP_E_INVALID_ARGUMENT), then the interpolator's
+ *     own checks (SDSP_E_COEFFICIENTS_LENGTH_ZERO, filters = 0 reported as
+ *     SDSP_E_INTERPOLATION_LESS_THAN_ONE, the device).  *out is null after
+ *     every failure.
+ *   Sub-filter length K (computed in f32), zero padding of the taps, the
+ *     branch layout and the window of the last K inputs per channel are
+ *     sdsp_interp_create's.  There is no scale.
+ *   Channels are channel-major and share step and t: input [channels][n],
+ *     output [channels][n_out].
+ *   Algorithms, set as sdsp_pfb_set_algo does: SDSP_ALGO_EXACT (both dot
+ *     products in the reference order; the subtraction, the product with mu
+ *     and the addition each rounded once, nothing contracted: bit-identical to
+ *     the same formula applied on the host to the EXACT interpolator's output)
+ *     and SDSP_ALGO_FMA (fused dot products, the last line fma(mu, c - a, a)).
+ *     New handles follow the process default as interpolators do.
+ *   Block entry points only: stream ordering, host staging, the refusal of
+ *     overlapping blocks and the error strings follow
+ *     sdsp_pfb_execute_block[_device].  A call that emits nothing (n_out = 0)
+ *     still moves the window and t.
+ * ------------------------------------------------------------------------ */
+typedef struct sdsp_arb sdsp_arb;
+SDSP_API int sdsp_arb_create(sdsp_arb** out, int dtype, const void* taps, size_t len, size_t filters, uint64_t step,
+                             int device);
+SDSP_API void sdsp_arb_destroy(sdsp_arb* h);
+/* same taps, algorithm, kernel knob, window, step and t */
+SDSP_API int sdsp_arb_clone(const sdsp_arb* h, sdsp_arb** out);
+/* zeroed window, t = 0; the step stays */
+SDSP_API int sdsp_arb_reset(sdsp_arb* h);
+SDSP_API int sdsp_arb_set_channels(sdsp_arb* h, size_t channels); /* zeroes the windows and t */
+SDSP_API int sdsp_arb_set_algo(sdsp_arb* h, int algo);
+SDSP_API int sdsp_arb_get_algo(const sdsp_arb* h);
+/* kernel-variant knob: SDSP_TUNE_ARB_KERNEL (performance only) */
+SDSP_API int sdsp_arb_set_tuning(sdsp_arb* h, int key, int value);
+SDSP_API size_t sdsp_arb_filters(const sdsp_arb* h);
+SDSP_API size_t sdsp_arb_subfilter_len(const sdsp_arb* h);
+SDSP_API int sdsp_arb_get_step(const sdsp_arb* h, uint64_t* step);
+/* takes effect at the next output; t stays unchanged.  Out of range: SDSP_E_INVALID_ARGUMENT */
+SDSP_API int sdsp_arb_set_step(sdsp_arb* h, uint64_t step);
+SDSP_API int sdsp_arb_get_time(const sdsp_arb* h, uint64_t* t);
+SDSP_API int sdsp_arb_set_time(sdsp_arb* h, uint64_t t); /* t >= 2^63: SDSP_E_INVALID_ARGUMENT */
+/* outputs per channel a block of n inputs produces from the handle's current step and t */
+SDSP_API size_t sdsp_arb_output_count(const sdsp_arb* h, size_t n);
+SDSP_API int sdsp_arb_execute_block(sdsp_arb* h, const void* in, size_t n, void* out, size_t* n_out);
+SDSP_API int sdsp_arb_execute_block_device(sdsp_arb* h, const void* d_in, size_t n, void* d_out, size_t* n_out,
+                                           void* stream);
+/* the kernel the next call runs (1 staged, 2 per output) and its outputs per workgroup */
+SDSP_API int sdsp_arb_info(const sdsp_arb* h, int* kernel, size_t* tile);
+SDSP_API int sdsp_arb_synchronize(sdsp_arb* h);
+/* The two formulas above (n_out and the next t) in 64-bit arithmetic; needs no handle and no
+ * device; both results are optional.  SDSP_E_INVALID_ARGUMENT when step is out of range,
+ * t >= 2^63 or n >= 2^31. */
+SDSP_API int sdsp_arb_count(uint64_t step, uint64_t t, size_t n, size_t* n_out, uint64_t* next_t);
+/* step = floor(ldexp(1.0 / rate, 32) + 0.5).  SDSP_E_INVALID_ARGUMENT for a rate that is not
+ * finite, is not positive, or whose step leaves the range (and for a null step). */
+SDSP_API int sdsp_arb_step_from_rate(double rate, uint64_t* step);
 
 /* ------------------------------------------------------------------------
  * AGC (src/auto_gain_control/mod.rs:97-677), SURVEY §8f row 4.  A handle is a

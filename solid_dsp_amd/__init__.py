@@ -27,6 +27,8 @@ from . import duc  # noqa: F401
 from .duc import DUC  # noqa: F401
 from . import resamp  # noqa: F401
 from .resamp import Resampler  # noqa: F401
+from . import arb  # noqa: F401
+from .arb import ArbResampler  # noqa: F401
 from .filter import (Filter, FIRFilter, DecimatingFIRFilter, PolyPhaseFilterBank,  # noqa: F401
                      InterpolatingFIRFilter, IIRFilter, IIRFilterType, SecondOrderFilter, DecimatingIIRFilter,
                      InterpolatingIIRFilter)

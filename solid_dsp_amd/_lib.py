@@ -28,6 +28,7 @@ TUNE_OLS_LONG_LOG2N, TUNE_OLS_LONG_SEGS = 22, 23
 TUNE_RESAMP_KERNEL = 24
 TUNE_ICHAN_KERNEL, TUNE_ICHAN_FRAMES_PER_BLOCK = 25, 26
 TUNE_OSCHAN_KERNEL, TUNE_OSCHAN_FRAMES_PER_BLOCK = 27, 28
+TUNE_ARB_KERNEL = 29
 
 _PAIRS = {
     (np.dtype(np.float32), np.dtype(np.float32)): RR32,
@@ -78,6 +79,7 @@ _lib = None
 def _declare(L):
     vp, sz, i, d, dp, szp = C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_size_t)
     vpp = C.POINTER(C.c_void_p)
+    u64, u64p = C.c_uint64, C.POINTER(C.c_uint64)
     sig = {
         "sdsp_last_error": (C.c_char_p, []),
         "sdsp_version": (C.c_char_p, []),
@@ -195,6 +197,28 @@ def _declare(L):
         "sdsp_resamp_info": (i, [vp, C.POINTER(i), szp]),
         "sdsp_resamp_synchronize": (i, [vp]),
         "sdsp_resamp_count": (i, [sz, sz, sz, sz, szp, szp]),
+        # arbitrary-rate resampler (linear interpolation between two polyphase branches, Q32.32 time)
+        "sdsp_arb_create": (i, [vpp, i, vp, sz, sz, u64, i]),
+        "sdsp_arb_destroy": (None, [vp]),
+        "sdsp_arb_clone": (i, [vp, vpp]),
+        "sdsp_arb_reset": (i, [vp]),
+        "sdsp_arb_set_channels": (i, [vp, sz]),
+        "sdsp_arb_set_algo": (i, [vp, i]),
+        "sdsp_arb_get_algo": (i, [vp]),
+        "sdsp_arb_set_tuning": (i, [vp, i, i]),
+        "sdsp_arb_filters": (sz, [vp]),
+        "sdsp_arb_subfilter_len": (sz, [vp]),
+        "sdsp_arb_get_step": (i, [vp, u64p]),
+        "sdsp_arb_set_step": (i, [vp, u64]),
+        "sdsp_arb_get_time": (i, [vp, u64p]),
+        "sdsp_arb_set_time": (i, [vp, u64]),
+        "sdsp_arb_output_count": (sz, [vp, sz]),
+        "sdsp_arb_execute_block": (i, [vp, vp, sz, vp, szp]),
+        "sdsp_arb_execute_block_device": (i, [vp, vp, sz, vp, szp, vp]),
+        "sdsp_arb_info": (i, [vp, C.POINTER(i), szp]),
+        "sdsp_arb_synchronize": (i, [vp]),
+        "sdsp_arb_count": (i, [u64, u64, sz, szp, u64p]),
+        "sdsp_arb_step_from_rate": (i, [d, u64p]),
         # synthesis channeliser (inverse FFT fused into the polyphase bank)
         "sdsp_ichan_create": (i, [vpp, i, vp, sz, sz, i]),
         "sdsp_ichan_destroy": (None, [vp]),

@@ -313,6 +313,31 @@ struct ResampPlan {
 };
 ResampPlan resamp_plan(int dtype, int M, size_t D, int K, int forced);
 hipError_t launch_resamp(int dtype, const ResampArgs& a, hipStream_t s);
+// Arbitrary-rate resampler (kern_arb.hip): output k sits at time T = t + k step (Q32.32 input samples);
+// with j = T >> 32, v = (T & (2^32 - 1)) P, b = v >> 32 and mu = (v & (2^32 - 1)) 2^-32 it is
+// a + mu (c - a), c = z[j P + b] and a = z[j P + b - 1] of the interpolator's stream z above (M = P).
+constexpr int kArbStaged = 1, kArbPerOutput = 2;
+struct ArbArgs {
+    const void* x;     // [channels][n]
+    const void* hist;  // [channels][H] oldest first, as PfbArgs; H = K (a reaches x[j - K] when b = 0)
+    const void* cb;    // [P][K]
+    void* y;           // [channels][n_out]
+    size_t n, n_out, channels;
+    int K, P, H;
+    uint64_t step, t;  // inputs per output and time of output 0, Q32.32 (sdsp_arb_count keeps every T < 2^63)
+    bool exact;
+    int kernel;        // SDSP_TUNE_ARB_KERNEL: 0 automatic, or a kArb* value
+};
+// which kernel a shape runs on and how it is tiled: a function of the shape and the step, never of n or t
+struct ArbPlan {
+    int kernel;   // kArbStaged / kArbPerOutput
+    size_t tile;  // outputs per workgroup
+    int S;        // staged: samples of the LDS span, for the largest fraction a tile can start on
+    bool cb_lds;  // staged: branch table in LDS
+    size_t lds;   // dynamic LDS bytes
+};
+ArbPlan arb_plan(int dtype, int P, uint64_t step, int K, int forced);
+hipError_t launch_arb(int dtype, const ArbArgs& a, hipStream_t s);
 // AGC bank (src/auto_gain_control/mod.rs): state is sdsp_agc_state[channels] in
 // device memory; cplx = Complex<f64> samples, else f64
 // pipe: agc_pipe_kernel for calls it admits (SDSP_TUNE_AGC_KERNEL 0), else agc_kernel
