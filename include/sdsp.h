@@ -386,6 +386,11 @@ SDSP_API int sdsp_fft_execute_device(sdsp_fft* h, const void* d_in, void* d_out,
  * Appendix A.6).  M channels (power of two, 4..4096), K = len / M taps per
  * branch, branch p fed by input phase M-1-p.  dtype SDSP_RC32 or SDSP_RC64.
  * Blocks are whole frames: n (per stream) a multiple of M; out[s][frame][M].
+ * sdsp_chan_create refuses, in this order and before any device work: a null
+ * `out`, another dtype (SDSP_E_UNSUPPORTED), a null `taps` with len > 0
+ * (SDSP_E_INVALID_ARGUMENT), channels = 0, len = 0, a channel count that is no
+ * power of two in 4..4096 (SDSP_E_UNSUPPORTED), len < channels; then a missing
+ * device.  sdsp_ichan_create and sdsp_oschan_create check in the same order.
  * ------------------------------------------------------------------------ */
 typedef struct sdsp_chan sdsp_chan;
 SDSP_API int sdsp_chan_create(sdsp_chan** out, int dtype, const void* taps, size_t len, size_t channels,

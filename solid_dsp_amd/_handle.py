@@ -6,9 +6,10 @@ include/sdsp.h).  ``FirHandle`` adds what the streaming FIR family has in
 common (``_FirBase``, ``PolyPhaseFilterBank``, ``DDC``, ``DUC``, ``Resampler``):
 clone, reset, synchronize, the constructor's dtype prologue and the host block
 marshalling.  The configuration methods that only some of these classes have
-(``set_channels``, ``set_algo``, ``get_algo``, ``set_tuning``) are written once
-below and bound by the classes whose C family has the function, and the NCO
-setters of the two converters come from ``Oscillator``.
+(``set_channels``, ``set_algo``, ``get_algo``, ``set_tuning``, ``info``) are
+written once below and bound by the classes whose C family has the function, and
+the NCO setters of the two converters come from ``Oscillator``.  ``ChanHandle``
+is the base of the three channelisers.
 """
 from __future__ import annotations
 
@@ -117,6 +118,60 @@ def get_algo(self) -> int:
 def set_tuning(self, key: int, value: int):
     """kernel-variant knobs (SDSP_TUNE_*, include/sdsp.h): performance only"""
     self._call("set_tuning", int(key), int(value))
+
+
+def info(self):
+    """(kernel, frames_per_block): the kernel the next call runs (the class's KERNELS) and its frames
+    per workgroup on a long block"""
+    k, f = C.c_int(), C.c_size_t()
+    self._call("info", C.byref(k), C.byref(f))
+    return k.value, f.value
+
+
+class ChanHandle(Handle):
+    """The channeliser family (``Channelizer``, ``ChannelSynthesizer``, ``OversampledChannelizer``): M
+    channels, real taps and complex samples, one frame every ``_step`` time samples (M, or D)."""
+
+    def _create(self, taps, channels, sample_dtype, device, streams, *stride):
+        """sdsp_<family>_create(&h, dtype, taps, len, channels, *stride, device), then the streams"""
+        self.dtype = L.RC32 if np.dtype(sample_dtype) == np.complex64 else L.RC64
+        self.coef_dtype = L.COEF_DTYPE[self.dtype]
+        self.sample_dtype = L.SAMPLE_DTYPE[self.dtype]
+        t = np.ascontiguousarray(taps, dtype=self.coef_dtype)
+        h = C.c_void_p()
+        L.check(getattr(L.lib(), f"sdsp_{self._family}_create")(
+            C.byref(h), self.dtype, L.ptr(t) if len(t) else None, len(t), channels, *stride, device))
+        self._h = h
+        self.M = channels
+        self._step = stride[0] if stride else channels
+        self.device = device
+        self.streams = 1
+        if streams != 1:
+            self.set_streams(streams)
+
+    set_tuning = set_tuning
+
+    def set_streams(self, streams: int):
+        """zeroes the history and the frame phase"""
+        self._call("set_streams", streams)
+        self.streams = streams
+
+    def reset(self):
+        self._call("reset")
+
+    def synchronize(self):
+        self._call("synchronize")
+
+    def execute_block_device(self, d_in, n: int, d_out, stream=None) -> int:
+        """Device-resident block of n = frames * step samples per stream: [streams, n] time samples
+        and [streams, frames, M] channel samples, whichever way the family goes.  Returns the frame
+        count."""
+        fr = C.c_size_t(0)
+        pin = L.device_ptr(d_in, self.sample_dtype, self.streams * n, self.device, "input")
+        pout = L.device_ptr(d_out, self.sample_dtype, self.streams * (n // self._step) * self.M, self.device,
+                            "output")
+        self._call("execute_block_device", pin, n, pout, C.byref(fr), L.stream_handle(stream))
+        return fr.value
 
 
 class Oscillator:

@@ -15,6 +15,7 @@
 // into the LDS buffer the FFT runs in.
 #include <cstdlib>
 
+#include "sdsp_chan_dev.hpp"
 #include "sdsp_device.hpp"
 #include "sdsp_fft_dev.hpp"
 #include "sdsp_kernels.hpp"
@@ -278,7 +279,7 @@ hipError_t launch_fft(bool f64, const FftArgs& a, hipStream_t s) {
 template <typename T>
 hipError_t launch_chan_t(const ChanArgs& a, hipStream_t s) {
     const size_t lds = 2 * (size_t)a.M * sizeof(c2<T>);
-    const int thr = a.M >= 1024 ? 256 : (a.M >= 256 ? a.M / 4 : 64);
+    const int thr = chan_threads(a.M);
     dim3 grid((unsigned)a.frames, (unsigned)a.streams);
     hipLaunchKernelGGL((chan_kernel<T>), grid, dim3(thr), lds, s, (const c2<T>*)a.x, (const c2<T>*)a.hist,
                        (const T*)a.cb, (c2<T>*)a.y, (const c2<T>*)a.tw, a.M, a.logM, a.K, (long long)a.n);

@@ -22,6 +22,7 @@
 //   ichan_ring_kernel   grid (chunk of F frames, stream).  The K most recent transformed frames
 //                       stay in LDS: one HBM read, one transform and K multiply-adds per output
 //                       sample, (K-1)/F extra reads for the chunk's warm-up.
+#include "sdsp_chan_dev.hpp"
 #include "sdsp_device.hpp"
 #include "sdsp_fft_dev.hpp"
 #include "sdsp_kernels.hpp"
@@ -29,15 +30,6 @@
 namespace sdsp {
 
 namespace {
-
-constexpr size_t kIchanLdsCap = 128 * 1024;  // ring kernel: (K+1) M samples at most
-constexpr size_t kIchanLdsAll = 160 * 1024;  // LDS per CU: the ring plus, where it fits, the twiddle table
-
-template <typename T>
-__device__ __forceinline__ void ichan_mac(c2<T>& acc, T c, c2<T> v) {
-    acc.re = acc.re + c * v.re;
-    acc.im = acc.im + c * v.im;
-}
 
 // frame f of one stream: from the block, or from the history ([(K-1) M], oldest first) when f < 0
 template <typename T>
@@ -64,7 +56,7 @@ __device__ __forceinline__ void ichan_branch_step(c2<T> (&acc)[NPT], const T* __
 #pragma unroll
     for (int j = 0; j < NPT; ++j) {
         const int r = tid + j * nthr;
-        if (r < M) ichan_mac(acc[j], c[r], u[M - 1 - r]);
+        if (r < M) chan_mac(acc[j], c[r], u[M - 1 - r]);
     }
 }
 
@@ -176,7 +168,7 @@ ichan_ring_kernel(const c2<T>* __restrict__ x, const c2<T>* __restrict__ hist, c
 #pragma unroll
                     for (int j = 0; j < NPT; ++j) {
                         const int r = tid + j * nthr;
-                        if (r < M) ichan_mac(acc[j], cf[i][j], u[M - 1 - r]);
+                        if (r < M) chan_mac(acc[j], cf[i][j], u[M - 1 - r]);
                     }
                     sl = sl == 0 ? KC : sl - 1;
                 }
@@ -200,7 +192,7 @@ ichan_ring_kernel(const c2<T>* __restrict__ x, const c2<T>* __restrict__ hist, c
 
 // Which kernel a handle runs and the ring kernel's frames per workgroup on a long block: a
 // function of the shape and the two knobs alone (sdsp_ichan_info).
-//   kernel: the ring kernel where its K+1 slots fit kIchanLdsCap, unless the per-frame kernel is
+//   kernel: the ring kernel where its K+1 slots fit kChanLdsCap, unless the per-frame kernel is
 //           asked for; a ring request that does not fit runs the per-frame kernel.
 //   frames: the knob when set.  Automatic: max(128, 8 (K-1)).  The warm-up then re-reads at most an
 //           eighth of the input, 7/128 of it at K = 8, and a block of 2^17 frames is 1024
@@ -209,7 +201,7 @@ ichan_ring_kernel(const c2<T>* __restrict__ x, const c2<T>* __restrict__ hist, c
 //           cost 5 to 8 %, 8 frames 47 to 54 %, and 512 frames (256 workgroups at M = 1024) 42 to 60 %.
 IchanPlan ichan_plan(bool f64, int M, int K, int kernel, int frames_per_block) {
     const size_t sample = f64 ? 16 : 8;
-    const bool fits = ((size_t)K + 1) * (size_t)M * sample <= kIchanLdsCap;
+    const bool fits = ((size_t)K + 1) * (size_t)M * sample <= kChanLdsCap;
     IchanPlan p;
     p.kernel = kernel != kIchanPerFrame && fits ? kIchanRing : kIchanPerFrame;
     if (p.kernel == kIchanPerFrame) p.frames_per_block = 1;
@@ -228,56 +220,26 @@ hipError_t launch_ichan_n(const IchanArgs& a, const IchanPlan& p, int thr, hipSt
                            (const T*)a.cbt, (c2<T>*)a.y, (const c2<T>*)a.tw, a.M, a.logM, a.K, (long long)a.n);
         return hipGetLastError();
     }
-    // An automatic chunk shrinks on a block too short to give four workgroups to each of 256 CUs
-    // at the planned size, never below K frames (the warm-up then doubles the reads at most; the
-    // per-frame kernel reads and transforms K times).  A chunk set by the knob is taken as it is.
-    size_t F = p.frames_per_block;
-    if (a.frames_per_block <= 0) {
-        const size_t spread = (a.frames * a.streams + 1023) / 1024;
-        const size_t least = spread > (size_t)a.K ? spread : (size_t)a.K;
-        if (least < F) F = least;
-    }
-    if (F > a.frames) F = a.frames;
+    // never below K frames: the warm-up then doubles the reads at most (the per-frame kernel reads and
+    // transforms K times)
+    const size_t F = chunk_frames(p.frames_per_block, a.frames_per_block > 0, a.frames, a.streams, (size_t)a.K);
     dim3 grid((unsigned)((a.frames + F - 1) / F), (unsigned)a.streams);
     const size_t ring = ((size_t)a.K + 1) * a.M * sizeof(c2<T>), table = (size_t)a.M * sizeof(c2<T>);
-    const bool twl = ring + table <= kIchanLdsAll;  // (all but M = 4096, K = 1 in complex f64)
-#define SDSP_ICHAN_RING_TW(KC, TWL, LDS)                                                                        \
-    hipLaunchKernelGGL((ichan_ring_kernel<T, NPT, KC, TWL>), grid, dim3(thr), LDS, s, x, hist, (const T*)a.cbt, \
-                       (c2<T>*)a.y, (const c2<T>*)a.tw, a.M, a.logM, a.K, (long long)a.n, (long long)a.frames, \
-                       (int)F)
-#define SDSP_ICHAN_RING(KC)                                    \
-    do {                                                       \
-        if (twl) SDSP_ICHAN_RING_TW(KC, true, ring + table);   \
-        else SDSP_ICHAN_RING_TW(KC, false, ring);              \
-    } while (0)
-    switch (a.K) {
-        case 1: SDSP_ICHAN_RING(1); break;
-        case 2: SDSP_ICHAN_RING(2); break;
-        case 3: SDSP_ICHAN_RING(3); break;
-        case 4: SDSP_ICHAN_RING(4); break;
-        case 5: SDSP_ICHAN_RING(5); break;
-        case 6: SDSP_ICHAN_RING(6); break;
-        case 7: SDSP_ICHAN_RING(7); break;
-        case 8: SDSP_ICHAN_RING(8); break;
-        default: SDSP_ICHAN_RING(0); break;
-    }
-#undef SDSP_ICHAN_RING
-#undef SDSP_ICHAN_RING_TW
+    const bool twl = ring + table <= kChanLdsAll;  // (all but M = 4096, K = 1 in complex f64)
+    chan_dispatch_k(a.K, [&](auto kc) {
+        constexpr int KC = decltype(kc)::value;
+        const auto kernel = twl ? ichan_ring_kernel<T, NPT, KC, true> : ichan_ring_kernel<T, NPT, KC, false>;
+        hipLaunchKernelGGL(kernel, grid, dim3(thr), twl ? ring + table : ring, s, x, hist, (const T*)a.cbt,
+                           (c2<T>*)a.y, (const c2<T>*)a.tw, a.M, a.logM, a.K, (long long)a.n, (long long)a.frames,
+                           (int)F);
+    });
     return hipGetLastError();
 }
 
 template <typename T>
 hipError_t launch_ichan_t(const IchanArgs& a, const IchanPlan& p, hipStream_t s) {
-    // workgroup sizes as launch_chan_t; NPT outputs per lane cover the frame
-    const int thr = a.M >= 1024 ? 256 : (a.M >= 256 ? a.M / 4 : 64);
-    switch ((a.M + thr - 1) / thr) {
-        case 1: return launch_ichan_n<T, 1>(a, p, thr, s);
-        case 2: return launch_ichan_n<T, 2>(a, p, thr, s);
-        case 4: return launch_ichan_n<T, 4>(a, p, thr, s);
-        case 8: return launch_ichan_n<T, 8>(a, p, thr, s);
-        case 16: return launch_ichan_n<T, 16>(a, p, thr, s);
-    }
-    return hipErrorInvalidValue;  // M is a power of two in [4, 4096]: not reached
+    const int thr = chan_threads(a.M);  // NPT outputs per lane cover the frame
+    return chan_dispatch_npt(a.M, thr, [&](auto npt) { return launch_ichan_n<T, decltype(npt)::value>(a, p, thr, s); });
 }
 
 hipError_t launch_ichan(bool f64, const IchanArgs& a, hipStream_t s) {

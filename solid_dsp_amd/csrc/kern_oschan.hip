@@ -27,6 +27,7 @@
 //   oschan_slide_kernel  grid (chunk of F frames, stream).  A ring of K M + D samples of the stream
 //                        stays in LDS and advances by D samples per frame: one HBM read per input
 //                        sample, (K M - D) / (F D) extra for the chunk's fill.
+#include "sdsp_chan_dev.hpp"
 #include "sdsp_device.hpp"
 #include "sdsp_fft_dev.hpp"
 #include "sdsp_kernels.hpp"
@@ -35,15 +36,7 @@ namespace sdsp {
 
 namespace {
 
-constexpr size_t kOschanLdsCap = 128 * 1024;  // sliding kernel: the ring and the Stockham pair at most
-constexpr size_t kOschanLdsAll = 160 * 1024;  // LDS per CU: those plus, where it fits, the twiddle table
 constexpr size_t kOschanLdsAuto = 16 * 1024;  // automatic choice: the sliding kernel up to this footprint
-
-template <typename T>
-__device__ __forceinline__ void oschan_mac(c2<T>& acc, T c, c2<T> v) {
-    acc.re = acc.re + c * v.re;
-    acc.im = acc.im + c * v.im;
-}
 
 // sample j of one stream's call: from the block, or from the history ([H], oldest first) when j < 0
 template <typename T>
@@ -79,7 +72,7 @@ oschan_frame_kernel(const c2<T>* __restrict__ x, const c2<T>* __restrict__ hist,
     for (int p = threadIdx.x; p < M; p += blockDim.x) {
         c2<T> acc = {T(0), T(0)};
         for (int i = 0; i < K; ++i)
-            oschan_mac(acc, cbt[(long long)i * M + p], oschan_sample(x, hist, e - p - (long long)i * M, H));
+            chan_mac(acc, cbt[(long long)i * M + p], oschan_sample(x, hist, e - p - (long long)i * M, H));
         a[(p - sh) & (M - 1)] = acc;
     }
     __syncthreads();
@@ -179,13 +172,13 @@ oschan_slide_kernel(const c2<T>* __restrict__ x, const c2<T>* __restrict__ hist,
                 if constexpr (KC > 0) {
 #pragma unroll
                     for (int i = 0; i < KC; ++i) {
-                        oschan_mac(acc, cf[i][j], ring[q]);
+                        chan_mac(acc, cf[i][j], ring[q]);
                         q -= M;
                         if (q < 0) q += cap;
                     }
                 } else {
                     for (int i = 0; i < K; ++i) {
-                        oschan_mac(acc, cbt[(long long)i * M + p], ring[q]);
+                        chan_mac(acc, cbt[(long long)i * M + p], ring[q]);
                         q -= M;
                         if (q < 0) q += cap;
                     }
@@ -209,7 +202,7 @@ oschan_slide_kernel(const c2<T>* __restrict__ x, const c2<T>* __restrict__ hist,
 // Which kernel a handle runs and the sliding kernel's frames per workgroup on a long block: a
 // function of the shape and the two knobs alone (sdsp_oschan_info).
 //   kernel: a sliding request runs the sliding kernel where its ring (K M + D samples) and the
-//           Stockham pair (2 M) fit kOschanLdsCap, else the per-frame kernel.  Automatic is the
+//           Stockham pair (2 M) fit kChanLdsCap, else the per-frame kernel.  Automatic is the
 //           sliding kernel where ring, pair and table take at most kOschanLdsAuto, ten workgroups to
 //           a CU.  Measured at K = 8, D = M/2, complex f32: the sliding kernel
 //           takes 0.72 and 0.80 of the per-frame kernel's time at M = 64 and 128 (6 and 12 KiB), the
@@ -222,7 +215,7 @@ oschan_slide_kernel(const c2<T>* __restrict__ x, const c2<T>* __restrict__ hist,
 OschanPlan oschan_plan(bool f64, int M, int K, int D, int kernel, int frames_per_block) {
     const size_t sample = f64 ? 16 : 8;
     const size_t base = ((size_t)K * M + (size_t)D + 2 * (size_t)M) * sample;
-    const bool fits = base <= kOschanLdsCap, pays = base + (size_t)M * sample <= kOschanLdsAuto;
+    const bool fits = base <= kChanLdsCap, pays = base + (size_t)M * sample <= kOschanLdsAuto;
     OschanPlan p;
     p.kernel = (kernel == kOschanSlide && fits) || (kernel == 0 && pays) ? kOschanSlide : kOschanPerFrame;
     if (p.kernel == kOschanPerFrame) p.frames_per_block = 1;
@@ -245,60 +238,30 @@ hipError_t launch_oschan_n(const OschanArgs& a, const OschanPlan& p, int thr, hi
                            (long long)a.n, (long long)a.frames);
         return hipGetLastError();
     }
-    // An automatic chunk shrinks on a block too short to give four workgroups to each of 256 CUs at
-    // the planned size, never below the fill's own length in frames (the fill then doubles the reads
-    // at most).  A chunk set by the knob is taken as it is.  (Reasoned, not measured.)
-    size_t F = p.frames_per_block;
-    if (a.frames_per_block <= 0) {
-        const size_t spread = (a.frames * a.streams + 1023) / 1024;
-        const size_t fill = ((size_t)a.K * a.M - 1) / a.D;  // ceil((K M - D) / D)
-        const size_t least = spread > fill ? spread : fill;  // (spread >= 1)
-        if (least < F) F = least;
-    }
-    if (F > a.frames) F = a.frames;
+    // never below the fill's own length in frames, ceil((K M - D) / D): the fill then doubles the
+    // reads at most.  (Reasoned, not measured.)
+    const size_t F = chunk_frames(p.frames_per_block, a.frames_per_block > 0, a.frames, a.streams,
+                                  ((size_t)a.K * a.M - 1) / a.D);
     dim3 grid((unsigned)((a.frames + F - 1) / F), (unsigned)a.streams);
     const size_t base = ((size_t)a.K * a.M + a.D + 2 * (size_t)a.M) * sizeof(c2<T>);
     const size_t table = (size_t)a.M * sizeof(c2<T>);
-    const bool twl = base + table <= kOschanLdsAll;
-#define SDSP_OSCHAN_SLIDE_TW(KC, TWL, LDS)                                                                        \
-    hipLaunchKernelGGL((oschan_slide_kernel<T, NPT, KC, TWL>), grid, dim3(thr), LDS, s, x, hist, (const T*)a.cbt, \
-                       (c2<T>*)a.y, (const c2<T>*)a.tw, a.M, a.logM, a.K, a.D, a.phase, (long long)a.n,          \
-                       (long long)a.frames, (int)F)
-    // (K NPT > 40 fits no precision's 128 KiB: those depths get no register instance of their own)
-#define SDSP_OSCHAN_SLIDE(K_)                                  \
-    do {                                                       \
-        constexpr int KC = K_ * NPT <= 40 ? K_ : 0;            \
-        if (twl) SDSP_OSCHAN_SLIDE_TW(KC, true, base + table); \
-        else SDSP_OSCHAN_SLIDE_TW(KC, false, base);            \
-    } while (0)
-    switch (a.K) {
-        case 1: SDSP_OSCHAN_SLIDE(1); break;
-        case 2: SDSP_OSCHAN_SLIDE(2); break;
-        case 3: SDSP_OSCHAN_SLIDE(3); break;
-        case 4: SDSP_OSCHAN_SLIDE(4); break;
-        case 5: SDSP_OSCHAN_SLIDE(5); break;
-        case 6: SDSP_OSCHAN_SLIDE(6); break;
-        case 7: SDSP_OSCHAN_SLIDE(7); break;
-        case 8: SDSP_OSCHAN_SLIDE(8); break;
-        default: SDSP_OSCHAN_SLIDE(0); break;
-    }
-#undef SDSP_OSCHAN_SLIDE
-#undef SDSP_OSCHAN_SLIDE_TW
+    const bool twl = base + table <= kChanLdsAll;
+    chan_dispatch_k(a.K, [&](auto k) {
+        // (K NPT > 40 fits no precision's 128 KiB: those depths get no register instance of their own)
+        constexpr int KC = decltype(k)::value * NPT <= 40 ? decltype(k)::value : 0;
+        const auto kernel = twl ? oschan_slide_kernel<T, NPT, KC, true> : oschan_slide_kernel<T, NPT, KC, false>;
+        hipLaunchKernelGGL(kernel, grid, dim3(thr), twl ? base + table : base, s, x, hist, (const T*)a.cbt,
+                           (c2<T>*)a.y, (const c2<T>*)a.tw, a.M, a.logM, a.K, a.D, a.phase, (long long)a.n,
+                           (long long)a.frames, (int)F);
+    });
     return hipGetLastError();
 }
 
 template <typename T>
 hipError_t launch_oschan_t(const OschanArgs& a, const OschanPlan& p, hipStream_t s) {
-    // workgroup sizes as launch_chan_t; NPT branches per lane cover the frame
-    const int thr = a.M >= 1024 ? 256 : (a.M >= 256 ? a.M / 4 : 64);
-    switch ((a.M + thr - 1) / thr) {
-        case 1: return launch_oschan_n<T, 1>(a, p, thr, s);
-        case 2: return launch_oschan_n<T, 2>(a, p, thr, s);
-        case 4: return launch_oschan_n<T, 4>(a, p, thr, s);
-        case 8: return launch_oschan_n<T, 8>(a, p, thr, s);
-        case 16: return launch_oschan_n<T, 16>(a, p, thr, s);
-    }
-    return hipErrorInvalidValue;  // M is a power of two in [4, 4096]: not reached
+    const int thr = chan_threads(a.M);  // NPT branches per lane cover the frame
+    return chan_dispatch_npt(a.M, thr,
+                             [&](auto npt) { return launch_oschan_n<T, decltype(npt)::value>(a, p, thr, s); });
 }
 
 hipError_t launch_oschan(bool f64, const OschanArgs& a, hipStream_t s) {

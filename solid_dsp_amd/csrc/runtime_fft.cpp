@@ -124,35 +124,182 @@ struct sdsp_fft : HandleCore {
     DevBuf work, tmp;   // device scratch, grown with the batch
 };
 
-struct sdsp_chan : HandleCore {
-    int dtype = SDSP_RC32;
-    size_t M = 0, K = 0, streams = 1;
-    std::vector<unsigned char> taps;
-    DevBuf cb, tw;
-    PingPong hist;  // [streams][(K-1) M] oldest first
-    int fast = 5;  // streaming M = 1024 kernel variant (SDSP_TUNE_CHAN_STREAMING): 8-frame rounds
-    int fpb = 0;       // its frames per workgroup (SDSP_TUNE_CHAN_FRAMES_PER_BLOCK, 0 = default)
-    bool xcd = true;   // XCD-contiguous chunk order (SDSP_TUNE_CHAN_XCD_ORDER)
+// The strings of a channeliser family that differ from its siblings'
+struct ChanText {
+    const char *dtype, *block, *overlap;  // refusals: create's dtype, a block's length, an in-place block
+    const char *create, *launch;          // what a device error names
 };
 
-struct sdsp_ichan : HandleCore {
+// What the three channeliser handles share: an M-point power-of-two transform and a K-deep
+// polyphase bank over frames `step` samples apart (M for sdsp_chan and sdsp_ichan, D <= M for
+// sdsp_oschan).  A block of n samples per stream is n / step frames and frames * M outputs; the
+// history keeps the K M - step samples before the block, which is (K-1) M at step = M.
+struct ChanCore : HandleCore {
+    const ChanText* text = nullptr;
     int dtype = SDSP_RC32;
-    size_t M = 0, K = 0, streams = 1;
-    DevBuf cbt, tw;  // cbt[i][r] = g[r + (K-1-i) M], [K][M]
-    PingPong hist;   // [streams][(K-1) M] input frames (untransformed), oldest first
-    int kernel = 0;  // SDSP_TUNE_ICHAN_KERNEL
-    int fpb = 0;     // SDSP_TUNE_ICHAN_FRAMES_PER_BLOCK
+    size_t M = 0, K = 0, step = 0, streams = 1;
+    DevBuf table, tw;  // the branch coefficients in the family's layout; make_twiddles(M)
+    PingPong hist;     // [streams][K M - step] input samples, oldest first
+    size_t phase = 0;  // (samples so far) mod M: stays 0 at step = M
+    int kernel = 0;    // SDSP_TUNE_*CHAN_KERNEL
+    int fpb = 0;       // SDSP_TUNE_*CHAN_FRAMES_PER_BLOCK
+
+    // create's argument checks in their one order, then the device
+    static int check(const ChanText& t, int dtype, const void* taps, size_t len, size_t M, size_t step, int device) {
+        if (dtype != SDSP_RC32 && dtype != SDSP_RC64) { set_error(t.dtype); return SDSP_E_UNSUPPORTED; }
+        if (!taps && len > 0) { set_error("taps pointer is null"); return SDSP_E_INVALID_ARGUMENT; }
+        if (M == 0) { set_error("FIR Filter Error NotEnoughFilters"); return SDSP_E_NOT_ENOUGH_FILTERS; }
+        if (len == 0) { set_error("FIR Filter Error CoefficientsLengthZero"); return SDSP_E_COEFFICIENTS_LENGTH_ZERO; }
+        if (!is_pow2(M) || M < 4 || M > 4096) {
+            set_error("channel count must be a power of two in [4, 4096]");
+            return SDSP_E_UNSUPPORTED;
+        }
+        if (step == 0 || step > M) {  // (sdsp_oschan's D; M itself for the other two)
+            set_error("decimation (the frame stride) must be in [1, channels]");
+            return SDSP_E_UNSUPPORTED;
+        }
+        if (len < M) { set_error("fewer taps than channels"); return SDSP_E_INVALID_ARGUMENT; }
+        return check_device(device, nullptr);
+    }
+    // Checked arguments -> a handle with one stream of zero history.  Row i of the table is the taps'
+    // block K-1-i, cbt[i][p] = h[p + (K-1-i) M] ([K][M]); `by_branch` stores its transpose,
+    // cb[p][i] ([M][K], pfb.rs:33-40).  Taps beyond K M are ignored.
+    int init(const ChanText& t, int dt, const void* taps, size_t len, size_t channels, size_t stride, bool by_branch,
+             int dev) {
+        text = &t;
+        dtype = dt;
+        M = channels;
+        K = len / M;
+        step = stride;
+        const size_t cbytes = coef_bytes(dtype);
+        const unsigned char* src = (const unsigned char*)taps;
+        std::vector<unsigned char> tab(K * M * cbytes);
+        for (size_t i = 0; i < K; ++i)
+            for (size_t p = 0; p < M; ++p)
+                std::memcpy(&tab[(by_branch ? p * K + i : i * M + p) * cbytes], src + (p + (K - 1 - i) * M) * cbytes,
+                            cbytes);
+        hipError_t e = open(dev);
+        if (e == hipSuccess) e = table.ensure(tab.size());
+        if (e == hipSuccess) e = hipMemcpy(table.p, tab.data(), tab.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return device_status(e, t.create);
+        const int st = make_twiddles(tw, M, dtype == SDSP_RC64);
+        return st ? st : set_streams(1);
+    }
+    // also the reset: zero history in both halves, phase 0, nothing queued
+    int set_streams(size_t count) {
+        if (count == 0) return SDSP_E_INVALID_ARGUMENT;
+        DeviceGuard g(device);
+        SDSP_TRY(fence.wait(), "wait for queued work");  // a queued block may still read the history
+        streams = count;
+        SDSP_TRY(hist.reset(streams * (K * M - step) * sample_bytes(dtype), stream), "zero history");
+        phase = 0;
+        return quiesce();
+    }
+    int synchronize() const {
+        DeviceGuard g(device);
+        return quiesce();
+    }
+    // One device block of n samples per stream on the caller's stream (or the handle's):
+    // launch(d_in, n, frames, d_out, stream) -> hipError_t queues the family's kernel, which reads
+    // hist.front() and `phase`; then the history moves on by the n inputs.
+    template <typename Launch>
+    int block_device(const void* d_in, size_t n, void* d_out, size_t* frames, void* user_stream, Launch launch) {
+        if (n % step) { set_error(text->block); return SDSP_E_INVALID_ARGUMENT; }
+        const size_t fr = n / step;
+        if (frames) *frames = fr;
+        if (fr == 0) return SDSP_OK;
+        const size_t sb = streams * sample_bytes(dtype);
+        if (ranges_overlap(d_in, n * sb, d_out, fr * M * sb)) {
+            set_error(text->overlap);
+            return SDSP_E_INVALID_ARGUMENT;
+        }
+        DeviceGuard g(device);
+        hipStream_t s = pick(user_stream, stream);
+        SDSP_TRY(fence.order_before(s), "order after queued work");  // the history this launch reads
+        SDSP_TRY(launch(d_in, n, fr, d_out, s), text->launch);
+        SDSP_TRY(launch_hist_update(dtype, d_in, hist.front(), hist.back(), n, (int)(K * M - step), streams, s),
+                 "history update");
+        hist.flip();
+        phase = (phase + n) % M;
+        SDSP_TRY(fence.record(s), "record fence");
+        return SDSP_OK;
+    }
+    // The host-slice twin: [streams][n] in and [streams][frames][M] out through the staging buffers
+    template <typename Launch> int block_host(const void* in, size_t n, void* out, size_t* frames, Launch launch) {
+        DeviceGuard g(device);
+        if (n % step) { set_error(text->block); return SDSP_E_INVALID_ARGUMENT; }
+        const size_t fr = n / step, sb = streams * sample_bytes(dtype);
+        if (frames) *frames = fr;
+        if (n == 0) return SDSP_OK;
+        return staged(in, n * sb, out, fr * M * sb, [&](const void* d_in, void* d_out, hipStream_t s) {
+            return block_device(d_in, n, d_out, nullptr, s, launch);
+        });
+    }
 };
 
-struct sdsp_oschan : HandleCore {
-    int dtype = SDSP_RC32;
-    size_t M = 0, K = 0, D = 0, streams = 1;
-    DevBuf cbt, tw;    // cbt[i][p] = h[p + (K-1-i) M], [K][M]
-    PingPong hist;     // [streams][K M - D] input samples, oldest first
-    size_t phase = 0;  // (frames so far * D) mod M
-    int kernel = 0;    // SDSP_TUNE_OSCHAN_KERNEL
-    int fpb = 0;       // SDSP_TUNE_OSCHAN_FRAMES_PER_BLOCK
+// *_create: null `out`, the checks, then a handle of type H on `device`
+template <typename H>
+int chan_create(H** out, const ChanText& t, int dtype, const void* taps, size_t len, size_t M, size_t step,
+                bool by_branch, int device) {
+    if (!out) return SDSP_E_INVALID_ARGUMENT;
+    *out = nullptr;
+    int st = ChanCore::check(t, dtype, taps, len, M, step, device);
+    if (st) return st;
+    DeviceGuard g(device);
+    H* h = new H();
+    st = h->init(t, dtype, taps, len, M, step, by_branch, device);
+    if (st) { destroy_handle(h); return st; }
+    *out = h;
+    return SDSP_OK;
+}
+
+struct sdsp_chan : ChanCore {
+    int fast = 5;     // streaming M = 1024 kernel variant (SDSP_TUNE_CHAN_STREAMING): 8-frame rounds
+    bool xcd = true;  // XCD-contiguous chunk order (SDSP_TUNE_CHAN_XCD_ORDER)
+    auto launcher() {
+        return [this](const void* d_in, size_t n, size_t fr, void* d_out, hipStream_t s) {
+            ChanArgs a{d_in, hist.front(), table.p, d_out, tw.p, (int)M, ilog2(M), (int)K, n, fr, streams};
+            a.fast = fast;
+            a.frames_per_block = fpb;
+            a.xcd_order = xcd;
+            return launch_chan(dtype == SDSP_RC64, a, s);
+        };
+    }
 };
+
+struct sdsp_ichan : ChanCore {  // (the history holds untransformed input frames)
+    auto launcher() {
+        return [this](const void* d_in, size_t n, size_t fr, void* d_out, hipStream_t s) {
+            const IchanArgs a{d_in, hist.front(), table.p, d_out, tw.p, (int)M, ilog2(M), (int)K,
+                              n, fr, streams, kernel, fpb};
+            return launch_ichan(dtype == SDSP_RC64, a, s);
+        };
+    }
+};
+
+struct sdsp_oschan : ChanCore {
+    auto launcher() {
+        return [this](const void* d_in, size_t n, size_t fr, void* d_out, hipStream_t s) {
+            const OschanArgs a{d_in, hist.front(), table.p, d_out, tw.p, (int)M, ilog2(M), (int)K,
+                               (int)step, (int)phase, n, fr, streams, kernel, fpb};
+            return launch_oschan(dtype == SDSP_RC64, a, s);
+        };
+    }
+};
+
+constexpr ChanText kChanText{"channeliser takes real taps and complex samples (SDSP_RC32 / SDSP_RC64)",
+                             "channeliser blocks must be a whole number of M-sample frames",
+                             "input and output blocks overlap (in-place channelising is not supported)",
+                             "chan create", "channeliser"};
+constexpr ChanText kIchanText{"synthesis channeliser takes real taps and complex samples (SDSP_RC32 / SDSP_RC64)",
+                              "synthesis channeliser blocks must be a whole number of M-sample frames",
+                              "input and output blocks overlap (in-place synthesis is not supported)",
+                              "ichan create", "synthesis channeliser"};
+constexpr ChanText kOschanText{
+    "oversampled channeliser takes real taps and complex samples (SDSP_RC32 / SDSP_RC64)",
+    "oversampled channeliser blocks must be a whole number of D-sample frame strides",
+    "input and output blocks overlap (in-place channelising is not supported)",
+    "oschan create", "oversampled channeliser"};
 
 extern "C" {
 
@@ -281,54 +428,13 @@ int sdsp_fft_execute(sdsp_fft* h, const void* in, void* out, size_t batch) {
 
 // ---- channeliser -----------------------------------------------------------
 int sdsp_chan_create(sdsp_chan** out, int dtype, const void* taps, size_t len, size_t M, int device) {
-    if (!out) return SDSP_E_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (dtype != SDSP_RC32 && dtype != SDSP_RC64) {
-        set_error("channeliser takes real taps and complex samples (SDSP_RC32 / SDSP_RC64)");
-        return SDSP_E_UNSUPPORTED;
-    }
-    if (M == 0) { set_error("FIR Filter Error NotEnoughFilters"); return SDSP_E_NOT_ENOUGH_FILTERS; }
-    if (len == 0) { set_error("FIR Filter Error CoefficientsLengthZero"); return SDSP_E_COEFFICIENTS_LENGTH_ZERO; }
-    if (!is_pow2(M) || M < 4 || M > 4096) {
-        set_error("channel count must be a power of two in [4, 4096]");
-        return SDSP_E_UNSUPPORTED;
-    }
-    const size_t K = len / M;
-    if (K == 0) { set_error("fewer taps than channels"); return SDSP_E_INVALID_ARGUMENT; }
-    int st = check_device(device, nullptr);
-    if (st) return st;
-    DeviceGuard g(device);
-    sdsp_chan* h = new sdsp_chan();
-    h->dtype = dtype;
-    h->M = M;
-    h->K = K;
-    const size_t cbytes = coef_bytes(dtype);
-    h->taps.assign((const unsigned char*)taps, (const unsigned char*)taps + len * cbytes);
-    // branch coefficients, stored order: cb[p][K-1-idx] = h[p + idx M]   (pfb.rs:33-40)
-    std::vector<unsigned char> cb(M * K * cbytes);
-    for (size_t p = 0; p < M; ++p)
-        for (size_t idx = 0; idx < K; ++idx)
-            std::memcpy(&cb[(p * K + (K - 1 - idx)) * cbytes], &h->taps[(p + idx * M) * cbytes], cbytes);
-    hipError_t e = h->open(device);
-    if (e == hipSuccess) e = h->cb.ensure(cb.size());
-    if (e == hipSuccess) e = hipMemcpy(h->cb.p, cb.data(), cb.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { st = device_status(e, "chan create"); sdsp_chan_destroy(h); return st; }
-    st = make_twiddles(h->tw, M, dtype == SDSP_RC64);
-    if (!st) st = sdsp_chan_set_streams(h, 1);
-    if (st) { sdsp_chan_destroy(h); return st; }
-    *out = h;
-    return SDSP_OK;
+    return chan_create(out, kChanText, dtype, taps, len, M, M, true, device);
 }
 
 void sdsp_chan_destroy(sdsp_chan* h) { destroy_handle(h); }
 
 int sdsp_chan_set_streams(sdsp_chan* h, size_t streams) {
-    if (!h || streams == 0) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuard g(h->device);
-    SDSP_TRY(h->fence.wait(), "wait for queued work");  // a queued block may still read the history
-    h->streams = streams;
-    SDSP_TRY(h->hist.reset(streams * (h->K - 1) * h->M * sample_bytes(h->dtype), h->stream), "zero history");
-    return h->quiesce();
+    return h ? h->set_streams(streams) : SDSP_E_INVALID_ARGUMENT;
 }
 
 int sdsp_chan_set_tuning(sdsp_chan* h, int key, int value) {
@@ -340,108 +446,28 @@ int sdsp_chan_set_tuning(sdsp_chan* h, int key, int value) {
     return SDSP_OK;
 }
 
-int sdsp_chan_reset(sdsp_chan* h) { return h ? sdsp_chan_set_streams(h, h->streams) : SDSP_E_INVALID_ARGUMENT; }
+int sdsp_chan_reset(sdsp_chan* h) { return h ? h->set_streams(h->streams) : SDSP_E_INVALID_ARGUMENT; }
 
 int sdsp_chan_execute_block_device(sdsp_chan* h, const void* d_in, size_t n, void* d_out, size_t* frames,
                                    void* stream) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    if (n % h->M) {
-        set_error("channeliser blocks must be a whole number of M-sample frames");
-        return SDSP_E_INVALID_ARGUMENT;
-    }
-    const size_t fr = n / h->M;
-    if (frames) *frames = fr;
-    if (fr == 0) return SDSP_OK;
-    const size_t bytes = h->streams * n * sample_bytes(h->dtype);
-    if (ranges_overlap(d_in, bytes, d_out, bytes)) {
-        set_error("input and output blocks overlap (in-place channelising is not supported)");
-        return SDSP_E_INVALID_ARGUMENT;
-    }
-    DeviceGuard g(h->device);
-    hipStream_t s = pick(stream, h->stream);
-    SDSP_TRY(h->fence.order_before(s), "order after queued work");  // the history this launch reads
-    ChanArgs a{d_in, h->hist.front(), h->cb.p, d_out, h->tw.p, (int)h->M, ilog2(h->M), (int)h->K, n, fr, h->streams};
-    a.fast = h->fast;
-    a.frames_per_block = h->fpb;
-    a.xcd_order = h->xcd;
-    SDSP_TRY(launch_chan(h->dtype == SDSP_RC64, a, s), "channeliser");
-    const int H = (int)((h->K - 1) * h->M);
-    SDSP_TRY(launch_hist_update(h->dtype, d_in, h->hist.front(), h->hist.back(), n, H, h->streams, s),
-          "history update");
-    h->hist.flip();
-    SDSP_TRY(h->fence.record(s), "record fence");
-    return SDSP_OK;
+    return h ? h->block_device(d_in, n, d_out, frames, stream, h->launcher()) : SDSP_E_INVALID_ARGUMENT;
 }
 
 int sdsp_chan_execute_block(sdsp_chan* h, const void* in, size_t n, void* out, size_t* frames) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuard g(h->device);
-    const size_t bytes = h->streams * n * sample_bytes(h->dtype);
-    if (n % h->M) {
-        set_error("channeliser blocks must be a whole number of M-sample frames");
-        return SDSP_E_INVALID_ARGUMENT;
-    }
-    if (frames) *frames = n / h->M;
-    if (n == 0) return SDSP_OK;
-    return h->staged(in, bytes, out, bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
-        return sdsp_chan_execute_block_device(h, d_in, n, d_out, nullptr, s);
-    });
+    return h ? h->block_host(in, n, out, frames, h->launcher()) : SDSP_E_INVALID_ARGUMENT;
 }
 
-int sdsp_chan_synchronize(sdsp_chan* h) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuard g(h->device);
-    return h->quiesce();
-}
+int sdsp_chan_synchronize(sdsp_chan* h) { return h ? h->synchronize() : SDSP_E_INVALID_ARGUMENT; }
 
 // ---- synthesis channeliser ---------------------------------------------------
 int sdsp_ichan_create(sdsp_ichan** out, int dtype, const void* taps, size_t len, size_t M, int device) {
-    if (!out) return SDSP_E_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (dtype != SDSP_RC32 && dtype != SDSP_RC64) {
-        set_error("synthesis channeliser takes real taps and complex samples (SDSP_RC32 / SDSP_RC64)");
-        return SDSP_E_UNSUPPORTED;
-    }
-    if (!taps && len > 0) { set_error("taps pointer is null"); return SDSP_E_INVALID_ARGUMENT; }
-    if (M == 0) { set_error("FIR Filter Error NotEnoughFilters"); return SDSP_E_NOT_ENOUGH_FILTERS; }
-    if (len == 0) { set_error("FIR Filter Error CoefficientsLengthZero"); return SDSP_E_COEFFICIENTS_LENGTH_ZERO; }
-    if (!is_pow2(M) || M < 4 || M > 4096) {
-        set_error("channel count must be a power of two in [4, 4096]");
-        return SDSP_E_UNSUPPORTED;
-    }
-    const size_t K = len / M;
-    if (K == 0) { set_error("fewer taps than channels"); return SDSP_E_INVALID_ARGUMENT; }
-    int st = check_device(device, nullptr);
-    if (st) return st;
-    DeviceGuard g(device);
-    sdsp_ichan* h = new sdsp_ichan();
-    h->dtype = dtype;
-    h->M = M;
-    h->K = K;
-    // row i of the table is the taps' block K-1-i; taps beyond K M are ignored
-    const size_t row = M * coef_bytes(dtype);
-    std::vector<unsigned char> cbt(K * row);
-    for (size_t i = 0; i < K; ++i) std::memcpy(&cbt[i * row], (const unsigned char*)taps + (K - 1 - i) * row, row);
-    hipError_t e = h->open(device);
-    if (e == hipSuccess) e = h->cbt.ensure(cbt.size());
-    if (e == hipSuccess) e = hipMemcpy(h->cbt.p, cbt.data(), cbt.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { st = device_status(e, "ichan create"); sdsp_ichan_destroy(h); return st; }
-    st = make_twiddles(h->tw, M, dtype == SDSP_RC64);
-    if (!st) st = sdsp_ichan_set_streams(h, 1);
-    if (st) { sdsp_ichan_destroy(h); return st; }
-    *out = h;
-    return SDSP_OK;
+    return chan_create(out, kIchanText, dtype, taps, len, M, M, false, device);
 }
 
 void sdsp_ichan_destroy(sdsp_ichan* h) { destroy_handle(h); }
 
 int sdsp_ichan_set_streams(sdsp_ichan* h, size_t streams) {
-    if (!h || streams == 0) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuard g(h->device);
-    SDSP_TRY(h->fence.wait(), "wait for queued work");  // a queued block may still read the history
-    h->streams = streams;
-    SDSP_TRY(h->hist.reset(streams * (h->K - 1) * h->M * sample_bytes(h->dtype), h->stream), "zero history");
-    return h->quiesce();
+    return h ? h->set_streams(streams) : SDSP_E_INVALID_ARGUMENT;
 }
 
 int sdsp_ichan_set_tuning(sdsp_ichan* h, int key, int value) {
@@ -452,7 +478,7 @@ int sdsp_ichan_set_tuning(sdsp_ichan* h, int key, int value) {
     return SDSP_OK;
 }
 
-int sdsp_ichan_reset(sdsp_ichan* h) { return h ? sdsp_ichan_set_streams(h, h->streams) : SDSP_E_INVALID_ARGUMENT; }
+int sdsp_ichan_reset(sdsp_ichan* h) { return h ? h->set_streams(h->streams) : SDSP_E_INVALID_ARGUMENT; }
 
 size_t sdsp_ichan_channels(const sdsp_ichan* h) { return h ? h->M : 0; }
 size_t sdsp_ichan_subfilter_len(const sdsp_ichan* h) { return h ? h->K : 0; }
@@ -467,108 +493,24 @@ int sdsp_ichan_info(const sdsp_ichan* h, int* kernel, size_t* frames_per_block) 
 
 int sdsp_ichan_execute_block_device(sdsp_ichan* h, const void* d_in, size_t n, void* d_out, size_t* frames,
                                     void* stream) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    if (n % h->M) {
-        set_error("synthesis channeliser blocks must be a whole number of M-sample frames");
-        return SDSP_E_INVALID_ARGUMENT;
-    }
-    const size_t fr = n / h->M;
-    if (frames) *frames = fr;
-    if (fr == 0) return SDSP_OK;
-    const size_t bytes = h->streams * n * sample_bytes(h->dtype);
-    if (ranges_overlap(d_in, bytes, d_out, bytes)) {
-        set_error("input and output blocks overlap (in-place synthesis is not supported)");
-        return SDSP_E_INVALID_ARGUMENT;
-    }
-    DeviceGuard g(h->device);
-    hipStream_t s = pick(stream, h->stream);
-    SDSP_TRY(h->fence.order_before(s), "order after queued work");  // the history this launch reads
-    const IchanArgs a{d_in, h->hist.front(), h->cbt.p, d_out, h->tw.p, (int)h->M, ilog2(h->M), (int)h->K,
-                      n, fr, h->streams, h->kernel, h->fpb};
-    SDSP_TRY(launch_ichan(h->dtype == SDSP_RC64, a, s), "synthesis channeliser");
-    const int H = (int)((h->K - 1) * h->M);
-    SDSP_TRY(launch_hist_update(h->dtype, d_in, h->hist.front(), h->hist.back(), n, H, h->streams, s),
-          "history update");
-    h->hist.flip();
-    SDSP_TRY(h->fence.record(s), "record fence");
-    return SDSP_OK;
+    return h ? h->block_device(d_in, n, d_out, frames, stream, h->launcher()) : SDSP_E_INVALID_ARGUMENT;
 }
 
 int sdsp_ichan_execute_block(sdsp_ichan* h, const void* in, size_t n, void* out, size_t* frames) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuard g(h->device);
-    const size_t bytes = h->streams * n * sample_bytes(h->dtype);
-    if (n % h->M) {
-        set_error("synthesis channeliser blocks must be a whole number of M-sample frames");
-        return SDSP_E_INVALID_ARGUMENT;
-    }
-    if (frames) *frames = n / h->M;
-    if (n == 0) return SDSP_OK;
-    return h->staged(in, bytes, out, bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
-        return sdsp_ichan_execute_block_device(h, d_in, n, d_out, nullptr, s);
-    });
+    return h ? h->block_host(in, n, out, frames, h->launcher()) : SDSP_E_INVALID_ARGUMENT;
 }
 
-int sdsp_ichan_synchronize(sdsp_ichan* h) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuard g(h->device);
-    return h->quiesce();
-}
+int sdsp_ichan_synchronize(sdsp_ichan* h) { return h ? h->synchronize() : SDSP_E_INVALID_ARGUMENT; }
 
 // ---- oversampled analysis channeliser ----------------------------------------
 int sdsp_oschan_create(sdsp_oschan** out, int dtype, const void* taps, size_t len, size_t M, size_t D, int device) {
-    if (!out) return SDSP_E_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (dtype != SDSP_RC32 && dtype != SDSP_RC64) {
-        set_error("oversampled channeliser takes real taps and complex samples (SDSP_RC32 / SDSP_RC64)");
-        return SDSP_E_UNSUPPORTED;
-    }
-    if (!taps && len > 0) { set_error("taps pointer is null"); return SDSP_E_INVALID_ARGUMENT; }
-    if (M == 0) { set_error("FIR Filter Error NotEnoughFilters"); return SDSP_E_NOT_ENOUGH_FILTERS; }
-    if (len == 0) { set_error("FIR Filter Error CoefficientsLengthZero"); return SDSP_E_COEFFICIENTS_LENGTH_ZERO; }
-    if (!is_pow2(M) || M < 4 || M > 4096) {
-        set_error("channel count must be a power of two in [4, 4096]");
-        return SDSP_E_UNSUPPORTED;
-    }
-    if (D == 0 || D > M) {
-        set_error("decimation (the frame stride) must be in [1, channels]");
-        return SDSP_E_UNSUPPORTED;
-    }
-    const size_t K = len / M;
-    if (K == 0) { set_error("fewer taps than channels"); return SDSP_E_INVALID_ARGUMENT; }
-    int st = check_device(device, nullptr);
-    if (st) return st;
-    DeviceGuard g(device);
-    sdsp_oschan* h = new sdsp_oschan();
-    h->dtype = dtype;
-    h->M = M;
-    h->K = K;
-    h->D = D;
-    // row i of the table is the taps' block K-1-i; taps beyond K M are ignored
-    const size_t row = M * coef_bytes(dtype);
-    std::vector<unsigned char> cbt(K * row);
-    for (size_t i = 0; i < K; ++i) std::memcpy(&cbt[i * row], (const unsigned char*)taps + (K - 1 - i) * row, row);
-    hipError_t e = h->open(device);
-    if (e == hipSuccess) e = h->cbt.ensure(cbt.size());
-    if (e == hipSuccess) e = hipMemcpy(h->cbt.p, cbt.data(), cbt.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { st = device_status(e, "oschan create"); sdsp_oschan_destroy(h); return st; }
-    st = make_twiddles(h->tw, M, dtype == SDSP_RC64);
-    if (!st) st = sdsp_oschan_set_streams(h, 1);
-    if (st) { sdsp_oschan_destroy(h); return st; }
-    *out = h;
-    return SDSP_OK;
+    return chan_create(out, kOschanText, dtype, taps, len, M, D, false, device);
 }
 
 void sdsp_oschan_destroy(sdsp_oschan* h) { destroy_handle(h); }
 
 int sdsp_oschan_set_streams(sdsp_oschan* h, size_t streams) {
-    if (!h || streams == 0) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuard g(h->device);
-    SDSP_TRY(h->fence.wait(), "wait for queued work");  // a queued block may still read the history
-    h->streams = streams;
-    SDSP_TRY(h->hist.reset(streams * (h->K * h->M - h->D) * sample_bytes(h->dtype), h->stream), "zero history");
-    h->phase = 0;
-    return h->quiesce();
+    return h ? h->set_streams(streams) : SDSP_E_INVALID_ARGUMENT;
 }
 
 int sdsp_oschan_set_tuning(sdsp_oschan* h, int key, int value) {
@@ -579,16 +521,16 @@ int sdsp_oschan_set_tuning(sdsp_oschan* h, int key, int value) {
     return SDSP_OK;
 }
 
-int sdsp_oschan_reset(sdsp_oschan* h) { return h ? sdsp_oschan_set_streams(h, h->streams) : SDSP_E_INVALID_ARGUMENT; }
+int sdsp_oschan_reset(sdsp_oschan* h) { return h ? h->set_streams(h->streams) : SDSP_E_INVALID_ARGUMENT; }
 
 size_t sdsp_oschan_channels(const sdsp_oschan* h) { return h ? h->M : 0; }
-size_t sdsp_oschan_decimation(const sdsp_oschan* h) { return h ? h->D : 0; }
+size_t sdsp_oschan_decimation(const sdsp_oschan* h) { return h ? h->step : 0; }
 size_t sdsp_oschan_subfilter_len(const sdsp_oschan* h) { return h ? h->K : 0; }
 size_t sdsp_oschan_phase(const sdsp_oschan* h) { return h ? h->phase : 0; }
 
 int sdsp_oschan_info(const sdsp_oschan* h, int* kernel, size_t* frames_per_block) {
     if (!h) return SDSP_E_INVALID_ARGUMENT;
-    const OschanPlan p = oschan_plan(h->dtype == SDSP_RC64, (int)h->M, (int)h->K, (int)h->D, h->kernel, h->fpb);
+    const OschanPlan p = oschan_plan(h->dtype == SDSP_RC64, (int)h->M, (int)h->K, (int)h->step, h->kernel, h->fpb);
     if (kernel) *kernel = p.kernel;
     if (frames_per_block) *frames_per_block = p.frames_per_block;
     return SDSP_OK;
@@ -596,55 +538,14 @@ int sdsp_oschan_info(const sdsp_oschan* h, int* kernel, size_t* frames_per_block
 
 int sdsp_oschan_execute_block_device(sdsp_oschan* h, const void* d_in, size_t n, void* d_out, size_t* frames,
                                      void* stream) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    if (n % h->D) {
-        set_error("oversampled channeliser blocks must be a whole number of D-sample frame strides");
-        return SDSP_E_INVALID_ARGUMENT;
-    }
-    const size_t fr = n / h->D;
-    if (frames) *frames = fr;
-    if (fr == 0) return SDSP_OK;
-    const size_t sb = sample_bytes(h->dtype);
-    if (ranges_overlap(d_in, h->streams * n * sb, d_out, h->streams * fr * h->M * sb)) {
-        set_error("input and output blocks overlap (in-place channelising is not supported)");
-        return SDSP_E_INVALID_ARGUMENT;
-    }
-    DeviceGuard g(h->device);
-    hipStream_t s = pick(stream, h->stream);
-    SDSP_TRY(h->fence.order_before(s), "order after queued work");  // the history this launch reads
-    const OschanArgs a{d_in, h->hist.front(), h->cbt.p, d_out, h->tw.p, (int)h->M, ilog2(h->M), (int)h->K,
-                       (int)h->D, (int)h->phase, n, fr, h->streams, h->kernel, h->fpb};
-    SDSP_TRY(launch_oschan(h->dtype == SDSP_RC64, a, s), "oversampled channeliser");
-    const int H = (int)(h->K * h->M - h->D);
-    SDSP_TRY(launch_hist_update(h->dtype, d_in, h->hist.front(), h->hist.back(), n, H, h->streams, s),
-          "history update");
-    h->hist.flip();
-    h->phase = (h->phase + n) % h->M;  // n = frames * D
-    SDSP_TRY(h->fence.record(s), "record fence");
-    return SDSP_OK;
+    return h ? h->block_device(d_in, n, d_out, frames, stream, h->launcher()) : SDSP_E_INVALID_ARGUMENT;
 }
 
 int sdsp_oschan_execute_block(sdsp_oschan* h, const void* in, size_t n, void* out, size_t* frames) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuard g(h->device);
-    if (n % h->D) {
-        set_error("oversampled channeliser blocks must be a whole number of D-sample frame strides");
-        return SDSP_E_INVALID_ARGUMENT;
-    }
-    const size_t fr = n / h->D, sb = sample_bytes(h->dtype);
-    if (frames) *frames = fr;
-    if (n == 0) return SDSP_OK;
-    return h->staged(in, h->streams * n * sb, out, h->streams * fr * h->M * sb,
-                     [&](const void* d_in, void* d_out, hipStream_t s) {
-                         return sdsp_oschan_execute_block_device(h, d_in, n, d_out, nullptr, s);
-                     });
+    return h ? h->block_host(in, n, out, frames, h->launcher()) : SDSP_E_INVALID_ARGUMENT;
 }
 
-int sdsp_oschan_synchronize(sdsp_oschan* h) {
-    if (!h) return SDSP_E_INVALID_ARGUMENT;
-    DeviceGuard g(h->device);
-    return h->quiesce();
-}
+int sdsp_oschan_synchronize(sdsp_oschan* h) { return h ? h->synchronize() : SDSP_E_INVALID_ARGUMENT; }
 
 // ---- DotProduct ---------------------------------------------------------------
 // batch vectors of n samples (stride samples apart), coefficients as given to

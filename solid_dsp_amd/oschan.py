@@ -16,40 +16,19 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from ._handle import Handle, set_tuning
+from ._handle import ChanHandle, info
 
 
-class OversampledChannelizer(Handle):
+class OversampledChannelizer(ChanHandle):
     _family = "oschan"
     KERNELS = {1: "per_frame", 2: "sliding"}
 
     def __init__(self, taps, channels: int, decimation: int, sample_dtype=np.complex64, device=0, streams=1):
-        sdt = np.dtype(sample_dtype)
-        self.dtype = L.RC32 if sdt == np.complex64 else L.RC64
-        self.coef_dtype = L.COEF_DTYPE[self.dtype]
-        self.sample_dtype = L.SAMPLE_DTYPE[self.dtype]
-        t = np.ascontiguousarray(taps, dtype=self.coef_dtype)
-        h = C.c_void_p()
-        L.check(L.lib().sdsp_oschan_create(C.byref(h), self.dtype, L.ptr(t) if len(t) else None, len(t), channels,
-                                           decimation, device))
-        self._h = h
-        self.M = channels
+        self._create(taps, channels, sample_dtype, device, streams, decimation)
         self.D = decimation
-        self.device = device
-        self.streams = 1
-        if streams != 1:
-            self.set_streams(streams)
 
-    # L.TUNE_OSCHAN_KERNEL: 0 automatic, 1 per-frame, 2 sliding; L.TUNE_OSCHAN_FRAMES_PER_BLOCK
-    set_tuning = set_tuning
-
-    def set_streams(self, streams: int):
-        """zeroes the history and the frame phase"""
-        self._call("set_streams", streams)
-        self.streams = streams
-
-    def reset(self):
-        self._call("reset")
+    # set_tuning: L.TUNE_OSCHAN_KERNEL (0 automatic, 1 per-frame, 2 sliding), L.TUNE_OSCHAN_FRAMES_PER_BLOCK
+    info = info
 
     @property
     def K(self) -> int:
@@ -59,13 +38,6 @@ class OversampledChannelizer(Handle):
     def phase(self) -> int:
         """(frames so far * D) mod M"""
         return int(L.lib().sdsp_oschan_phase(self._h))
-
-    def info(self):
-        """(kernel, frames_per_block): the kernel the next call runs (1 per-frame, 2 sliding) and the
-        sliding kernel's frames per workgroup on a long block"""
-        k, f = C.c_int(), C.c_size_t()
-        self._call("info", C.byref(k), C.byref(f))
-        return k.value, f.value
 
     def execute_block(self, samples) -> np.ndarray:
         """[streams, n] (or [n]) time samples, n a multiple of D -> [streams, n/D, M] (or [n/D, M])"""
@@ -77,15 +49,3 @@ class OversampledChannelizer(Handle):
         fr = C.c_size_t(0)
         self._call("execute_block", L.ptr(x) if x.size else None, n, L.ptr(out) if out.size else None, C.byref(fr))
         return out
-
-    def execute_block_device(self, d_in, n: int, d_out, stream=None) -> int:
-        """Device-resident block of n = frames * D samples per stream, [streams, n] in and
-        [streams, frames, M] out; returns the frame count."""
-        fr = C.c_size_t(0)
-        pin = L.device_ptr(d_in, self.sample_dtype, self.streams * n, self.device, "input")
-        pout = L.device_ptr(d_out, self.sample_dtype, self.streams * (n // self.D) * self.M, self.device, "output")
-        self._call("execute_block_device", pin, n, pout, C.byref(fr), L.stream_handle(stream))
-        return fr.value
-
-    def synchronize(self):
-        self._call("synchronize")
