@@ -209,9 +209,13 @@ typedef enum {
                                       (sdsp_oschan_info) */
     SDSP_TUNE_OSCHAN_FRAMES_PER_BLOCK = 28, /* oversampled channeliser, sliding kernel: frames per workgroup,
                                       any value >= 1; 0 (default) = automatic */
-    SDSP_TUNE_ARB_KERNEL = 29      /* arbitrary-rate resampler: 0 (default) automatic, 1 staged kernel, 2 one
+    SDSP_TUNE_ARB_KERNEL = 29,     /* arbitrary-rate resampler: 0 (default) automatic, 1 staged kernel, 2 one
                                       lane per output; a value whose kernel does not apply to the handle's
                                       shape and step runs the automatic choice (sdsp_arb_info) */
+    SDSP_TUNE_ACORR_SLOTS = 30     /* AutoCorrelator, pipelined kernel: at most this many persistent waves
+                                      per channel (1..65536, rounded up to whole eights, one per XCD);
+                                      0 (default) = what the device holds resident.  Same results: fewer
+                                      waves walk more tiles each */
 } sdsp_tune_key;
 SDSP_API int sdsp_fir_set_tuning(sdsp_fir* h, int key, int value);
 SDSP_API void sdsp_fir_destroy(sdsp_fir* h);        /* Drop */
@@ -532,7 +536,7 @@ typedef struct sdsp_acorr sdsp_acorr;
 SDSP_API int sdsp_acorr_create(sdsp_acorr** out, size_t window_size, size_t delay, int precision, int device);
 SDSP_API void sdsp_acorr_destroy(sdsp_acorr* h);
 SDSP_API int sdsp_acorr_set_channels(sdsp_acorr* h, size_t channels);
-/* kernel-variant knob: SDSP_TUNE_ACORR_KERNEL (performance only) */
+/* kernel-variant knobs: SDSP_TUNE_ACORR_KERNEL, SDSP_TUNE_ACORR_SLOTS (performance only) */
 SDSP_API int sdsp_acorr_set_tuning(sdsp_acorr* h, int key, int value);
 SDSP_API size_t sdsp_acorr_window_size(const sdsp_acorr* h);
 SDSP_API size_t sdsp_acorr_delay(const sdsp_acorr* h);

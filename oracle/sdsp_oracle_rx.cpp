@@ -244,6 +244,10 @@ void orc_nco_state(void* h, uint32_t* theta, uint32_t* dtheta) {
     *theta = ((NCO*)h)->theta;
     *dtheta = ((NCO*)h)->delta_theta;
 }
+void orc_nco_set_state(void* h, uint32_t theta, uint32_t dtheta) {  // the two registers, as given
+    ((NCO*)h)->theta = theta;
+    ((NCO*)h)->delta_theta = dtheta;
+}
 void orc_nco_sincos(void* h, double* sc) { sc[0] = ((NCO*)h)->sin_(); sc[1] = ((NCO*)h)->cos_(); }
 int orc_nco_set_pll_bandwidth(void* h, double bw) {  // :124-132
     if (bw < 0.0) return 1;

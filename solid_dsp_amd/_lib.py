@@ -29,6 +29,7 @@ TUNE_RESAMP_KERNEL = 24
 TUNE_ICHAN_KERNEL, TUNE_ICHAN_FRAMES_PER_BLOCK = 25, 26
 TUNE_OSCHAN_KERNEL, TUNE_OSCHAN_FRAMES_PER_BLOCK = 27, 28
 TUNE_ARB_KERNEL = 29
+TUNE_ACORR_SLOTS = 30
 
 _PAIRS = {
     (np.dtype(np.float32), np.dtype(np.float32)): RR32,

@@ -721,7 +721,7 @@ static long long acorr_pipe_slots(int prec, size_t lds) {
 }
 
 hipError_t launch_acorr(int prec, const void* x, const void* hist, void* y, size_t n, int H, int d, int K,
-                        size_t channels, hipStream_t s, int kernel) {
+                        size_t channels, hipStream_t s, int kernel, int slots) {
     if (n == 0) return hipSuccess;
     dim3 grid((unsigned)((n + kOut - 1) / kOut), (unsigned)channels);
     const bool nostage = kernel == 2, pipe = kernel == 0;
@@ -735,7 +735,8 @@ hipError_t launch_acorr(int prec, const void* x, const void* hist, void* y, size
             const size_t lds2 = ((size_t)pad8(kOut + K - 1) + 1 + (size_t)(kOut + K - 1 + d)) * elem;
             // one persistent wave per resident slot (registers / LDS decide how many per CU): the
             // current device's CU count and the kernel's occupancy at this LDS size, cached
-            const long long res = acorr_pipe_slots(prec, lds2);
+            long long res = acorr_pipe_slots(prec, lds2);
+            if (slots > 0 && slots < res) res = slots;  // SDSP_TUNE_ACORR_SLOTS: fewer waves, more tiles each
             const long long nt = t_hi - t_lo;
             long long G = nt < res ? nt : res;
             G = (G + 7) / 8 * 8;  // whole workgroups per XCD (surplus ones find no tile and return)

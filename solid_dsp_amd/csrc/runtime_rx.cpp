@@ -53,6 +53,7 @@ struct sdsp_acorr : HandleCore {
     PingPong hist;   // [channels][W] oldest first
     DevBuf energy;   // [channels] f64
     int kernel = 0;  // SDSP_TUNE_ACORR_KERNEL
+    int slots = 0;   // SDSP_TUNE_ACORR_SLOTS (0: what the device holds resident)
     int K() const { return W > d ? (int)(W - d) : 0; }
 };
 
@@ -103,9 +104,16 @@ int sdsp_acorr_create(sdsp_acorr** out, size_t window_size, size_t delay, int pr
 void sdsp_acorr_destroy(sdsp_acorr* h) { destroy_handle(h); }
 
 int sdsp_acorr_set_tuning(sdsp_acorr* h, int key, int value) {
-    if (!h || key != SDSP_TUNE_ACORR_KERNEL || value < 0 || value > 2) return SDSP_E_INVALID_ARGUMENT;
-    h->kernel = value;
-    return SDSP_OK;
+    if (!h) return SDSP_E_INVALID_ARGUMENT;
+    if (key == SDSP_TUNE_ACORR_KERNEL && value >= 0 && value <= 2) {
+        h->kernel = value;
+        return SDSP_OK;
+    }
+    if (key == SDSP_TUNE_ACORR_SLOTS && value >= 0 && value <= 65536) {
+        h->slots = value;
+        return SDSP_OK;
+    }
+    return SDSP_E_INVALID_ARGUMENT;
 }
 
 int sdsp_acorr_set_channels(sdsp_acorr* h, size_t channels) {
@@ -131,7 +139,8 @@ static int acorr_run(sdsp_acorr* h, const void* d_in, size_t n, void* d_out, hip
     SDSP_TRY(h->fence.order_before(s), "order after queued work");
     const void* hist = h->hist.front();
     if (d_out)
-        SDSP_TRY(launch_acorr(h->prec, d_in, hist, d_out, n, (int)h->W, (int)h->d, h->K(), h->channels, s, h->kernel),
+        SDSP_TRY(launch_acorr(h->prec, d_in, hist, d_out, n, (int)h->W, (int)h->d, h->K(), h->channels, s, h->kernel,
+                              h->slots),
               "acorr");
     SDSP_TRY(launch_acorr_energy(h->prec, d_in, hist, n, (int)h->W, (int)h->W, h->channels, (double*)h->energy.p, s),
           "acorr energy");

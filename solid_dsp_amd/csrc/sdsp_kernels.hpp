@@ -256,8 +256,10 @@ hipError_t launch_dot(int dtype, const DotArgs& a, hipStream_t s);
 // kernel (SDSP_TUNE_ACORR_KERNEL): 0 the pipelined kernel on interior tiles where it applies, else the
 // one-shot kernel staging the delayed input in LDS; 1 the one-shot kernel everywhere (staged); 2 the
 // one-shot kernel with two loads per product (no staging)
+// slots (SDSP_TUNE_ACORR_SLOTS): 0 one pipelined wave per resident slot of the device, else at most
+// this many per channel (whole eights)
 hipError_t launch_acorr(int prec, const void* x, const void* hist, void* y, size_t n, int H, int d, int K,
-                        size_t channels, hipStream_t s, int kernel = 0);
+                        size_t channels, hipStream_t s, int kernel = 0, int slots = 0);
 hipError_t launch_acorr_current(int prec, const void* hist, void* out, int H, int d, int K, size_t channels,
                                 hipStream_t s);
 hipError_t launch_acorr_energy(int prec, const void* x, const void* hist, size_t n, int H, int W, size_t channels,

@@ -51,7 +51,10 @@ class AutoCorrelator(Handle):
         return x
 
     def set_tuning(self, key: int, value: int):
-        """Kernel-variant knob (L.TUNE_ACORR_KERNEL; performance only, same results)."""
+        """Kernel knobs (performance only, same results): L.TUNE_ACORR_KERNEL picks the kernel
+        variant (0..2); L.TUNE_ACORR_SLOTS caps the pipelined kernel's persistent waves per channel
+        (1..65536, rounded up to whole eights; 0 = what the device holds resident), so each wave
+        walks more tiles."""
         L.check(L.lib().sdsp_acorr_set_tuning(self._h, int(key), int(value)))
 
     def reset(self):  # :76-85

@@ -108,6 +108,7 @@ def lib():
         "orc_nco_adjust_phase": (None, [vp, C.c_double]),
         "orc_nco_reset": (None, [vp]),
         "orc_nco_state": (None, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "orc_nco_set_state": (None, [vp, C.c_uint32, C.c_uint32]),
         "orc_nco_sincos": (None, [vp, dp]),
         "orc_nco_set_pll_bandwidth": (C.c_int, [vp, C.c_double]),
         "orc_nco_pll_step": (None, [vp, C.c_double]),
