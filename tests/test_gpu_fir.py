@@ -668,9 +668,16 @@ def test_per_sample_execute_bit_parity(dt, cdt, sdt, L, M):
 @pytest.mark.parametrize("L,M,n1,n2", [(21, 3, 5000, 3333), (240, 24, 700, 9001), (3000, 1000, 9, 5),
                                        (6000, 2, 4100, 77), (12000, 2, 300, 50)])
 def test_pfb_staged_kernel_bit_parity(dt, cdt, sdt, L, M, n1, n2):
-    """the LDS-staged generic kernel (tiles of ~4096 outputs, coefficients staged when
-    they fit) and, for the longest branches, the per-output fallback: bit-identical to
-    the restatement over two calls (tile edges, history), for every dtype"""
+    """the LDS-staged generic kernel (tiles of ~4096 outputs, coefficients staged when they fit)
+    and, on the wider samples, the per-output fallback: bit-identical to the restatement over two
+    calls (tile edges, history).  By pfb_route's rule (restated in tests/pfb_cases.py, these shapes
+    classified in tests/test_pfb_cases.py) the first three shapes stage their branch taps in LDS
+    on every pair; (6000, 2) does so on RR32 only, reads them from global memory on RC32, CC32
+    and RR64 and runs the per-output kernel on RC64 and CC64; (12000, 2) runs the per-output
+    kernel on every pair but RR32, which stays on the staged kernel with its taps in global
+    memory (xb = 32192 bytes of samples): 4-byte samples leave it only at K >= 8194 (M = 1).
+    pfb_kernel<float, float, *> and the per-output kernel on several channels are run by
+    tests/test_gpu_pfb_paths.py"""
     rng = np.random.default_rng(L + M + dt)
     h = rand(rng, L, cdt)
     x = rand(rng, n1 + n2, sdt)
