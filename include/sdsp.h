@@ -212,10 +212,15 @@ typedef enum {
     SDSP_TUNE_ARB_KERNEL = 29,     /* arbitrary-rate resampler: 0 (default) automatic, 1 staged kernel, 2 one
                                       lane per output; a value whose kernel does not apply to the handle's
                                       shape and step runs the automatic choice (sdsp_arb_info) */
-    SDSP_TUNE_ACORR_SLOTS = 30     /* AutoCorrelator, pipelined kernel: at most this many persistent waves
+    SDSP_TUNE_ACORR_SLOTS = 30,    /* AutoCorrelator, pipelined kernel: at most this many persistent waves
                                       per channel (1..65536, rounded up to whole eights, one per XCD);
                                       0 (default) = what the device holds resident.  Same results: fewer
                                       waves walk more tiles each */
+    SDSP_TUNE_SPEC_KERNEL = 31,    /* spectrometer: 0 (default) automatic, 1 per-frame kernel, 2 sliding
+                                      kernel (the stream's window kept in LDS); a value whose kernel does
+                                      not fit the handle's shape runs the automatic choice (sdsp_spec_info) */
+    SDSP_TUNE_SPEC_SUBBLOCKS = 32  /* spectrometer: sub-blocks (of up to 32 frames) per workgroup, any
+                                      value >= 1; 0 (default) = automatic */
 } sdsp_tune_key;
 SDSP_API int sdsp_fir_set_tuning(sdsp_fir* h, int key, int value);
 SDSP_API void sdsp_fir_destroy(sdsp_fir* h);        /* Drop */
@@ -394,7 +399,7 @@ SDSP_API int sdsp_fft_execute_device(sdsp_fft* h, const void* d_in, void* d_out,
  * `out`, another dtype (SDSP_E_UNSUPPORTED), a null `taps` with len > 0
  * (SDSP_E_INVALID_ARGUMENT), channels = 0, len = 0, a channel count that is no
  * power of two in 4..4096 (SDSP_E_UNSUPPORTED), len < channels; then a missing
- * device.  sdsp_ichan_create and sdsp_oschan_create check in the same order.
+ * device.  sdsp_ichan_create, sdsp_oschan_create and sdsp_spec_create check in the same order.
  * ------------------------------------------------------------------------ */
 typedef struct sdsp_chan sdsp_chan;
 SDSP_API int sdsp_chan_create(sdsp_chan** out, int dtype, const void* taps, size_t len, size_t channels,
@@ -508,6 +513,73 @@ SDSP_API int sdsp_oschan_execute_block_device(sdsp_oschan* h, const void* d_in, 
  * device at it), 1 on the per-frame kernel.  Either pointer may be null */
 SDSP_API int sdsp_oschan_info(const sdsp_oschan* h, int* kernel, size_t* frames_per_block);
 SDSP_API int sdsp_oschan_synchronize(sdsp_oschan* h);
+
+/* ------------------------------------------------------------------------
+ * Spectrometer: integrated power spectra of the oversampled channeliser's
+ * frames, |Y|^2 summed inside the kernel (build-defined).  K = 1 with the taps
+ * a window is Welch's method at hop D; K > 1 is the polyphase spectrometer.
+ * Taps, channels M, decimation D and dtype as sdsp_oschan_create, checked in
+ * the same order; after the decimation check and before "fewer taps than
+ * channels", integration A must lie in 1..32768 (SDSP_E_UNSUPPORTED): longer
+ * integrations are the caller's sum of finished spectra, M values per 32768
+ * frames.  T is the dtype's real type.  Per stream, with m the frame index
+ * since create / reset / set_streams:
+ *
+ *     Y[m]    = frame m of sdsp_oschan with the same taps, M and D: the same
+ *               bits, index rotation and carried frame phase included
+ *     p[m][k] = Y.re * Y.re + Y.im * Y.im        (two rounded products, one rounded sum)
+ *
+ * Spectrum j integrates frames jA .. jA + A - 1 in sub-blocks of 32 frames
+ * counted from frame jA, the last one shorter when 32 does not divide A:
+ *
+ *     s_b[k] = ((0 + p[jA + 32 b][k]) + p[jA + 32 b + 1][k]) + ..      sequential, rounded in T
+ *     P_j[k] = (((0 + s_0) + s_1) + ..) * scale      sequential over at most 1024 sub-blocks,
+ *                                                    then one rounded multiply
+ *
+ * scale is a real T, 1 after create; sdsp_spec_set_scale rounds its argument
+ * to T, applies to spectra completed afterwards and survives reset.  One
+ * definition of the arithmetic: every kernel, every sub-blocks-per-workgroup
+ * value and every call split gives the same bits.
+ *
+ * Blocks: n (per stream) a multiple of D gives frames = n / D; the call emits
+ * spectra = (filled + frames) / A whole spectra, filled being the frames in the
+ * open integration (0 <= filled < A, sdsp_spec_filled), as out[s][spectrum][M]
+ * in T.  n = 0 is a no-op; a call that emits nothing may pass a null output;
+ * input and output may not overlap; a refused call changes no state.  State
+ * per stream: sdsp_oschan's K M - D sample history and frame phase, the open
+ * sub-block's running sum, the running sum of the open integration's closed
+ * sub-blocks, and filled; all zero after create, reset and set_streams.
+ * ------------------------------------------------------------------------ */
+typedef struct sdsp_spec sdsp_spec;
+SDSP_API int sdsp_spec_create(sdsp_spec** out, int dtype, const void* taps, size_t len, size_t channels,
+                              size_t decimation, size_t integration, int device);
+SDSP_API void sdsp_spec_destroy(sdsp_spec* h);
+SDSP_API int sdsp_spec_set_streams(sdsp_spec* h, size_t streams);
+/* kernel-variant knobs: SDSP_TUNE_SPEC_KERNEL, SDSP_TUNE_SPEC_SUBBLOCKS (performance only) */
+SDSP_API int sdsp_spec_set_tuning(sdsp_spec* h, int key, int value);
+SDSP_API int sdsp_spec_reset(sdsp_spec* h);
+SDSP_API int sdsp_spec_set_scale(sdsp_spec* h, double scale);
+SDSP_API size_t sdsp_spec_channels(const sdsp_spec* h);      /* M */
+SDSP_API size_t sdsp_spec_decimation(const sdsp_spec* h);    /* D */
+SDSP_API size_t sdsp_spec_subfilter_len(const sdsp_spec* h); /* K */
+SDSP_API size_t sdsp_spec_integration(const sdsp_spec* h);   /* A */
+SDSP_API size_t sdsp_spec_phase(const sdsp_spec* h);         /* (frames so far * D) mod M, as sdsp_oschan_phase */
+SDSP_API size_t sdsp_spec_filled(const sdsp_spec* h);        /* frames in the open integration; 0 for a null handle */
+/* host [streams][n] in, [streams][spectra][M] reals out through the staging buffers; *spectra (may be
+ * null) receives the count */
+SDSP_API int sdsp_spec_execute_block(sdsp_spec* h, const void* in, size_t n, void* out, size_t* spectra);
+SDSP_API int sdsp_spec_execute_block_device(sdsp_spec* h, const void* d_in, size_t n, void* d_out, size_t* spectra,
+                                            void* stream);
+/* what the next call runs: *kernel = 1 per-frame, 2 sliding; *subblocks_per_workgroup on a long block
+ * (an automatic value shrinks on blocks too short to fill the device at it).  Either pointer may be null */
+SDSP_API int sdsp_spec_info(const sdsp_spec* h, int* kernel, size_t* subblocks_per_workgroup);
+SDSP_API int sdsp_spec_synchronize(sdsp_spec* h);
+/* The block arithmetic without a handle or a device: a block of n samples per stream that starts
+ * `filled` frames into an integration emits *spectra spectra and leaves *next_filled frames (either
+ * pointer may be null).  SDSP_E_INVALID_ARGUMENT for decimation = 0, integration outside 1..32768,
+ * filled >= integration or n no multiple of decimation */
+SDSP_API int sdsp_spec_count(size_t decimation, size_t integration, size_t filled, size_t n, size_t* spectra,
+                             size_t* next_filled);
 
 /* ------------------------------------------------------------------------
  * DotProduct (src/dot_product/mod.rs:37-171): DotProduct::new(&coefs, direction)

@@ -10,6 +10,7 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct sdsp_chan { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_ichan { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_oschan { _p: [u8; 0] }
+#[repr(C)] pub struct sdsp_spec { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_acorr { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_nco { _p: [u8; 0] }
 #[repr(C)] pub struct sdsp_agc { _p: [u8; 0] }
@@ -187,6 +188,27 @@ extern "C" {
                                             frames: *mut usize, stream: *mut c_void) -> c_int;
     pub fn sdsp_oschan_info(h: *const sdsp_oschan, kernel: *mut c_int, frames_per_block: *mut usize) -> c_int;
     pub fn sdsp_oschan_synchronize(h: *mut sdsp_oschan) -> c_int;
+    pub fn sdsp_spec_create(out: *mut *mut sdsp_spec, dtype: c_int, taps: *const c_void, len: usize,
+                            channels: usize, decimation: usize, integration: usize, device: c_int) -> c_int;
+    pub fn sdsp_spec_destroy(h: *mut sdsp_spec);
+    pub fn sdsp_spec_set_streams(h: *mut sdsp_spec, streams: usize) -> c_int;
+    pub fn sdsp_spec_set_tuning(h: *mut sdsp_spec, key: c_int, value: c_int) -> c_int;
+    pub fn sdsp_spec_reset(h: *mut sdsp_spec) -> c_int;
+    pub fn sdsp_spec_set_scale(h: *mut sdsp_spec, scale: f64) -> c_int;
+    pub fn sdsp_spec_channels(h: *const sdsp_spec) -> usize;
+    pub fn sdsp_spec_decimation(h: *const sdsp_spec) -> usize;
+    pub fn sdsp_spec_subfilter_len(h: *const sdsp_spec) -> usize;
+    pub fn sdsp_spec_integration(h: *const sdsp_spec) -> usize;
+    pub fn sdsp_spec_phase(h: *const sdsp_spec) -> usize;
+    pub fn sdsp_spec_filled(h: *const sdsp_spec) -> usize;
+    pub fn sdsp_spec_execute_block(h: *mut sdsp_spec, input: *const c_void, n: usize, out: *mut c_void,
+                                   spectra: *mut usize) -> c_int;
+    pub fn sdsp_spec_execute_block_device(h: *mut sdsp_spec, d_in: *const c_void, n: usize, d_out: *mut c_void,
+                                          spectra: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn sdsp_spec_info(h: *const sdsp_spec, kernel: *mut c_int, subblocks_per_workgroup: *mut usize) -> c_int;
+    pub fn sdsp_spec_synchronize(h: *mut sdsp_spec) -> c_int;
+    pub fn sdsp_spec_count(decimation: usize, integration: usize, filled: usize, n: usize, spectra: *mut usize,
+                           next_filled: *mut usize) -> c_int;
 
     // tap / loop-filter design (firdes/mod.rs:243-368, iirdes/pll/mod.rs:24-99)
     pub fn sdsp_kaiser_beta(stop_band_attenuation: f64) -> f64;

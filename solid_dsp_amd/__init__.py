@@ -16,6 +16,8 @@ from . import synthesizer  # noqa: F401
 from .synthesizer import ChannelSynthesizer  # noqa: F401
 from . import oschan  # noqa: F401
 from .oschan import OversampledChannelizer  # noqa: F401
+from . import spectrometer  # noqa: F401
+from .spectrometer import Spectrometer  # noqa: F401
 from . import nco  # noqa: F401
 from .nco import NCO, NCOError  # noqa: F401
 from . import auto_gain_control  # noqa: F401

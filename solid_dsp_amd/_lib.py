@@ -30,6 +30,7 @@ TUNE_ICHAN_KERNEL, TUNE_ICHAN_FRAMES_PER_BLOCK = 25, 26
 TUNE_OSCHAN_KERNEL, TUNE_OSCHAN_FRAMES_PER_BLOCK = 27, 28
 TUNE_ARB_KERNEL = 29
 TUNE_ACORR_SLOTS = 30
+TUNE_SPEC_KERNEL, TUNE_SPEC_SUBBLOCKS = 31, 32
 
 _PAIRS = {
     (np.dtype(np.float32), np.dtype(np.float32)): RR32,
@@ -245,6 +246,24 @@ def _declare(L):
         "sdsp_oschan_execute_block_device": (i, [vp, vp, sz, vp, szp, vp]),
         "sdsp_oschan_info": (i, [vp, C.POINTER(i), szp]),
         "sdsp_oschan_synchronize": (i, [vp]),
+        # spectrometer (|Y|^2 of the oversampled channeliser's frames, integrated in the kernel)
+        "sdsp_spec_create": (i, [vpp, i, vp, sz, sz, sz, sz, i]),
+        "sdsp_spec_destroy": (None, [vp]),
+        "sdsp_spec_set_streams": (i, [vp, sz]),
+        "sdsp_spec_set_tuning": (i, [vp, i, i]),
+        "sdsp_spec_reset": (i, [vp]),
+        "sdsp_spec_set_scale": (i, [vp, d]),
+        "sdsp_spec_channels": (sz, [vp]),
+        "sdsp_spec_decimation": (sz, [vp]),
+        "sdsp_spec_subfilter_len": (sz, [vp]),
+        "sdsp_spec_integration": (sz, [vp]),
+        "sdsp_spec_phase": (sz, [vp]),
+        "sdsp_spec_filled": (sz, [vp]),
+        "sdsp_spec_execute_block": (i, [vp, vp, sz, vp, szp]),
+        "sdsp_spec_execute_block_device": (i, [vp, vp, sz, vp, szp, vp]),
+        "sdsp_spec_info": (i, [vp, C.POINTER(i), szp]),
+        "sdsp_spec_synchronize": (i, [vp]),
+        "sdsp_spec_count": (i, [sz, sz, sz, sz, szp, szp]),
         "sdsp_synth_f32_device": (i, [vp, C.c_uint64, C.c_uint64, C.c_uint64, sz, vp]),
         "sdsp_bandwidth_copy_device": (i, [vp, vp, sz, vp]),
         "sdsp_firdes_kaiser": (i, [sz, d, d, d, dp]),

@@ -38,19 +38,6 @@ namespace {
 
 constexpr size_t kOschanLdsAuto = 16 * 1024;  // automatic choice: the sliding kernel up to this footprint
 
-// sample j of one stream's call: from the block, or from the history ([H], oldest first) when j < 0
-template <typename T>
-__device__ __forceinline__ c2<T> oschan_sample(const c2<T>* __restrict__ x, const c2<T>* __restrict__ hist,
-                                               long long j, long long H) {
-    return j >= 0 ? x[j] : hist[H + j];
-}
-
-// the rotation of the call's frame f
-__device__ __forceinline__ int oschan_shift(int c, long long f, int D, int M) {
-    return (int)(((unsigned long long)c + (unsigned long long)(f + 1) * (unsigned long long)D) &
-                 (unsigned long long)(M - 1));
-}
-
 }  // namespace
 
 template <typename T>

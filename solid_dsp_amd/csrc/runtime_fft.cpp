@@ -1,6 +1,6 @@
 // C-ABI runtime for FFT (src/fft/mod.rs:175-215), the PFB + FFT channeliser
 // (build-defined), its synthesis counterpart (sdsp_ichan), its oversampled form
-// (sdsp_oschan) and batched DotProduct::execute
+// (sdsp_oschan), the spectrometer on that form (sdsp_spec) and batched DotProduct::execute
 // (src/dot_product/mod.rs:153-171).
 #include <hip/hip_runtime.h>
 
@@ -124,6 +124,8 @@ struct sdsp_fft : HandleCore {
     DevBuf work, tmp;   // device scratch, grown with the batch
 };
 
+constexpr size_t kSpecMaxIntegration = 32768;  // 1024 sub-blocks of 32 frames
+
 // The strings of a channeliser family that differ from its siblings'
 struct ChanText {
     const char *dtype, *block, *overlap;  // refusals: create's dtype, a block's length, an in-place block
@@ -144,8 +146,9 @@ struct ChanCore : HandleCore {
     int kernel = 0;    // SDSP_TUNE_*CHAN_KERNEL
     int fpb = 0;       // SDSP_TUNE_*CHAN_FRAMES_PER_BLOCK
 
-    // create's argument checks in their one order, then the device
-    static int check(const ChanText& t, int dtype, const void* taps, size_t len, size_t M, size_t step, int device) {
+    // create's argument checks in their one order, then the device (`integration`: sdsp_spec's A, 1 elsewhere)
+    static int check(const ChanText& t, int dtype, const void* taps, size_t len, size_t M, size_t step, int device,
+                     size_t integration = 1) {
         if (dtype != SDSP_RC32 && dtype != SDSP_RC64) { set_error(t.dtype); return SDSP_E_UNSUPPORTED; }
         if (!taps && len > 0) { set_error("taps pointer is null"); return SDSP_E_INVALID_ARGUMENT; }
         if (M == 0) { set_error("FIR Filter Error NotEnoughFilters"); return SDSP_E_NOT_ENOUGH_FILTERS; }
@@ -156,6 +159,10 @@ struct ChanCore : HandleCore {
         }
         if (step == 0 || step > M) {  // (sdsp_oschan's D; M itself for the other two)
             set_error("decimation (the frame stride) must be in [1, channels]");
+            return SDSP_E_UNSUPPORTED;
+        }
+        if (integration == 0 || integration > kSpecMaxIntegration) {
+            set_error("integration must be in [1, 32768] frames (sum finished spectra for more)");
             return SDSP_E_UNSUPPORTED;
         }
         if (len < M) { set_error("fewer taps than channels"); return SDSP_E_INVALID_ARGUMENT; }
@@ -240,10 +247,10 @@ struct ChanCore : HandleCore {
 // *_create: null `out`, the checks, then a handle of type H on `device`
 template <typename H>
 int chan_create(H** out, const ChanText& t, int dtype, const void* taps, size_t len, size_t M, size_t step,
-                bool by_branch, int device) {
+                bool by_branch, int device, size_t integration = 1) {
     if (!out) return SDSP_E_INVALID_ARGUMENT;
     *out = nullptr;
-    int st = ChanCore::check(t, dtype, taps, len, M, step, device);
+    int st = ChanCore::check(t, dtype, taps, len, M, step, device, integration);
     if (st) return st;
     DeviceGuard g(device);
     H* h = new H();
@@ -287,6 +294,69 @@ struct sdsp_oschan : ChanCore {
     }
 };
 
+// The oversampled channeliser's frames squared and integrated A at a time.  On top of ChanCore's
+// history and phase: the open sub-block's sum, the open integration's closed sub-blocks and the
+// frames in the open integration, all zero after create, reset and set_streams; the scale survives.
+struct sdsp_spec : ChanCore {
+    size_t A = 1, filled = 0;
+    double scale = 1.0;  // rounded to the real type
+    int subblocks = 0;   // SDSP_TUNE_SPEC_SUBBLOCKS
+    PingPong sub, tot;   // [streams][M] reals each
+    DevBuf part;         // the call's closed sub-blocks, grown on demand
+
+    size_t real_bytes() const { return sample_bytes(dtype) / 2; }
+    int set_streams(size_t count) {
+        const int st = ChanCore::set_streams(count);
+        if (st) return st;
+        DeviceGuard g(device);
+        SDSP_TRY(sub.reset(streams * M * real_bytes(), stream), "zero sums");
+        SDSP_TRY(tot.reset(streams * M * real_bytes(), stream), "zero sums");
+        filled = 0;
+        return quiesce();
+    }
+    // One device block: ChanCore::block_device's order of steps, with spectra M reals per stream out
+    int block_device(const void* d_in, size_t n, void* d_out, size_t* spectra, void* user_stream) {
+        if (n % step) { set_error(text->block); return SDSP_E_INVALID_ARGUMENT; }
+        const size_t fr = n / step, sp = (filled + fr) / A;
+        if (spectra) *spectra = sp;
+        if (fr == 0) return SDSP_OK;
+        if (!d_in || (sp && !d_out)) { set_error("block pointer is null"); return SDSP_E_INVALID_ARGUMENT; }
+        if (ranges_overlap(d_in, n * streams * sample_bytes(dtype), d_out, sp * M * streams * real_bytes())) {
+            set_error(text->overlap);
+            return SDSP_E_INVALID_ARGUMENT;
+        }
+        DeviceGuard g(device);
+        hipStream_t s = pick(user_stream, stream);
+        // (a larger scratch frees the old one, which waits for the device)
+        SDSP_TRY(part.ensure(streams * spec_subblocks(filled, A, fr) * M * real_bytes()), "spectrometer scratch");
+        SDSP_TRY(fence.order_before(s), "order after queued work");
+        const SpecArgs a{d_in, hist.front(), table.p, tw.p, sub.front(), sub.back(), tot.front(), tot.back(),
+                         part.p, d_out, (int)M, ilog2(M), (int)K, (int)step, (int)phase, (int)A, (int)filled,
+                         scale, n, fr, streams, kernel, subblocks};
+        SDSP_TRY(launch_spec(dtype == SDSP_RC64, a, s), text->launch);
+        SDSP_TRY(launch_hist_update(dtype, d_in, hist.front(), hist.back(), n, (int)(K * M - step), streams, s),
+                 "history update");
+        hist.flip();
+        sub.flip();
+        tot.flip();
+        phase = (phase + n) % M;
+        filled = (filled + fr) % A;
+        SDSP_TRY(fence.record(s), "record fence");
+        return SDSP_OK;
+    }
+    int block_host(const void* in, size_t n, void* out, size_t* spectra) {
+        DeviceGuard g(device);
+        if (n % step) { set_error(text->block); return SDSP_E_INVALID_ARGUMENT; }
+        const size_t sp = (filled + n / step) / A;
+        if (spectra) *spectra = sp;
+        if (n == 0) return SDSP_OK;
+        return staged(in, n * streams * sample_bytes(dtype), out, sp * M * streams * real_bytes(),
+                      [&](const void* d_in, void* d_out, hipStream_t s) {
+                          return block_device(d_in, n, d_out, nullptr, s);
+                      });
+    }
+};
+
 constexpr ChanText kChanText{"channeliser takes real taps and complex samples (SDSP_RC32 / SDSP_RC64)",
                              "channeliser blocks must be a whole number of M-sample frames",
                              "input and output blocks overlap (in-place channelising is not supported)",
@@ -300,6 +370,12 @@ constexpr ChanText kOschanText{
     "oversampled channeliser blocks must be a whole number of D-sample frame strides",
     "input and output blocks overlap (in-place channelising is not supported)",
     "oschan create", "oversampled channeliser"};
+
+constexpr ChanText kSpecText{
+    "spectrometer takes real taps and complex samples (SDSP_RC32 / SDSP_RC64)",
+    "spectrometer blocks must be a whole number of D-sample frame strides",
+    "input and output blocks overlap",
+    "spec create", "spectrometer"};
 
 extern "C" {
 
@@ -546,6 +622,77 @@ int sdsp_oschan_execute_block(sdsp_oschan* h, const void* in, size_t n, void* ou
 }
 
 int sdsp_oschan_synchronize(sdsp_oschan* h) { return h ? h->synchronize() : SDSP_E_INVALID_ARGUMENT; }
+
+// ---- spectrometer --------------------------------------------------------------
+int sdsp_spec_create(sdsp_spec** out, int dtype, const void* taps, size_t len, size_t M, size_t D, size_t A,
+                     int device) {
+    int st = chan_create(out, kSpecText, dtype, taps, len, M, D, false, device, A);
+    if (st) return st;
+    (*out)->A = A;
+    st = (*out)->set_streams(1);  // the sums, which ChanCore::init knows nothing of
+    if (st) { destroy_handle(*out); *out = nullptr; }
+    return st;
+}
+
+void sdsp_spec_destroy(sdsp_spec* h) { destroy_handle(h); }
+
+int sdsp_spec_set_streams(sdsp_spec* h, size_t streams) {
+    return h ? h->set_streams(streams) : SDSP_E_INVALID_ARGUMENT;
+}
+
+int sdsp_spec_set_tuning(sdsp_spec* h, int key, int value) {
+    if (!h) return SDSP_E_INVALID_ARGUMENT;
+    if (key == SDSP_TUNE_SPEC_KERNEL && value >= 0 && value <= 2) h->kernel = value;
+    else if (key == SDSP_TUNE_SPEC_SUBBLOCKS && value >= 0) h->subblocks = value;
+    else return SDSP_E_INVALID_ARGUMENT;
+    return SDSP_OK;
+}
+
+int sdsp_spec_reset(sdsp_spec* h) { return h ? h->set_streams(h->streams) : SDSP_E_INVALID_ARGUMENT; }
+
+int sdsp_spec_set_scale(sdsp_spec* h, double scale) {
+    if (!h) return SDSP_E_INVALID_ARGUMENT;
+    h->scale = h->dtype == SDSP_RC64 ? scale : (double)(float)scale;  // read at each launch
+    return SDSP_OK;
+}
+
+size_t sdsp_spec_channels(const sdsp_spec* h) { return h ? h->M : 0; }
+size_t sdsp_spec_decimation(const sdsp_spec* h) { return h ? h->step : 0; }
+size_t sdsp_spec_subfilter_len(const sdsp_spec* h) { return h ? h->K : 0; }
+size_t sdsp_spec_integration(const sdsp_spec* h) { return h ? h->A : 0; }
+size_t sdsp_spec_phase(const sdsp_spec* h) { return h ? h->phase : 0; }
+size_t sdsp_spec_filled(const sdsp_spec* h) { return h ? h->filled : 0; }
+
+int sdsp_spec_info(const sdsp_spec* h, int* kernel, size_t* subblocks_per_workgroup) {
+    if (!h) return SDSP_E_INVALID_ARGUMENT;
+    const SpecPlan p = spec_plan(h->dtype == SDSP_RC64, (int)h->M, (int)h->K, (int)h->step, (int)h->A, h->kernel,
+                                 h->subblocks);
+    if (kernel) *kernel = p.kernel;
+    if (subblocks_per_workgroup) *subblocks_per_workgroup = p.subblocks;
+    return SDSP_OK;
+}
+
+int sdsp_spec_count(size_t decimation, size_t integration, size_t filled, size_t n, size_t* spectra,
+                    size_t* next_filled) {
+    if (decimation == 0 || integration == 0 || integration > kSpecMaxIntegration || filled >= integration ||
+        n % decimation)
+        return SDSP_E_INVALID_ARGUMENT;
+    const size_t total = filled + n / decimation;
+    if (spectra) *spectra = total / integration;
+    if (next_filled) *next_filled = total % integration;
+    return SDSP_OK;
+}
+
+int sdsp_spec_execute_block_device(sdsp_spec* h, const void* d_in, size_t n, void* d_out, size_t* spectra,
+                                   void* stream) {
+    return h ? h->block_device(d_in, n, d_out, spectra, stream) : SDSP_E_INVALID_ARGUMENT;
+}
+
+int sdsp_spec_execute_block(sdsp_spec* h, const void* in, size_t n, void* out, size_t* spectra) {
+    return h ? h->block_host(in, n, out, spectra) : SDSP_E_INVALID_ARGUMENT;
+}
+
+int sdsp_spec_synchronize(sdsp_spec* h) { return h ? h->synchronize() : SDSP_E_INVALID_ARGUMENT; }
 
 // ---- DotProduct ---------------------------------------------------------------
 // batch vectors of n samples (stride samples apart), coefficients as given to

@@ -1,6 +1,7 @@
-// What the fused channeliser kernels share (kern_ichan.hip, kern_oschan.hip): the branch sum's step,
-// the LDS budget and the launchers' dispatch and chunk rule; and the workgroup size of
-// all three channelisers (launch_chan_t in kern_fft.hip too).
+// What the fused channeliser kernels share (kern_ichan.hip, kern_oschan.hip, kern_spec.hip): the
+// branch sum's step, the oversampled walk's sample fetch and rotation, the LDS budget and the
+// launchers' dispatch and chunk rule; and the workgroup size of all three channelisers
+// (launch_chan_t in kern_fft.hip too).
 #pragma once
 #include <type_traits>
 
@@ -16,6 +17,19 @@ template <typename T>
 __device__ __forceinline__ void chan_mac(c2<T>& acc, T c, c2<T> v) {
     acc.re = acc.re + c * v.re;
     acc.im = acc.im + c * v.im;
+}
+
+// sample j of one stream's call: from the block, or from the history ([H], oldest first) when j < 0
+template <typename T>
+__device__ __forceinline__ c2<T> oschan_sample(const c2<T>* __restrict__ x, const c2<T>* __restrict__ hist,
+                                               long long j, long long H) {
+    return j >= 0 ? x[j] : hist[H + j];
+}
+
+// the rotation of the call's frame f
+__device__ __forceinline__ int oschan_shift(int c, long long f, int D, int M) {
+    return (int)(((unsigned long long)c + (unsigned long long)(f + 1) * (unsigned long long)D) &
+                 (unsigned long long)(M - 1));
 }
 
 // lanes per workgroup: 64 below M = 256, M / 4 at 256 and 512, 256 from 1024 up

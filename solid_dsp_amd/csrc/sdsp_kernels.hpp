@@ -241,6 +241,37 @@ struct OschanPlan {
 OschanPlan oschan_plan(bool f64, int M, int K, int D, int kernel, int frames_per_block);
 hipError_t launch_oschan(bool f64, const OschanArgs& a, hipStream_t s);
 
+// spectrometer (kern_spec.hip): the oversampled channeliser's frames squared and integrated A at a time
+constexpr int kSpecPerFrame = 1;  // branch sums from global memory, as kOschanPerFrame
+constexpr int kSpecSlide = 2;     // the stream's window kept in LDS, as kOschanSlide
+struct SpecArgs {
+    const void* x;       // [streams][n]
+    const void* hist;    // [streams][K M - D] input samples, oldest first
+    const void* cbt;     // [K][M] real branch coefficients, as OschanArgs
+    const void* tw;
+    const void* sub_in;  // [streams][M] reals: the open sub-block's running sum (read when filled % 32 > 0)
+    void* sub_out;       // the same after the call (written when the call ends inside a sub-block)
+    const void* tot_in;  // [streams][M] reals: the open integration's closed sub-blocks (read when filled >= 32)
+    void* tot_out;       // the same after the call (written when the call ends inside an integration)
+    void* part;          // scratch [streams][spec_subblocks()][M] reals
+    void* out;           // [streams][spectra][M] reals, spectra = (filled + frames) / A
+    int M, logM, K, D;
+    int phase;           // (frames before this call * D) mod M
+    int A, filled;       // integration length; frames in the open integration before the call, < A
+    double scale;        // already rounded to the real type
+    size_t n, frames, streams;
+    int kernel;          // SDSP_TUNE_SPEC_KERNEL: 0 automatic, or a kSpec* value
+    int subblocks;       // SDSP_TUNE_SPEC_SUBBLOCKS: sub-blocks per workgroup, 0 automatic
+};
+struct SpecPlan {
+    int kernel;        // kSpecPerFrame / kSpecSlide
+    size_t subblocks;  // sub-blocks (of up to 32 frames) per workgroup on a long block
+};
+SpecPlan spec_plan(bool f64, int M, int K, int D, int A, int kernel, int subblocks);
+// sub-blocks a call of `frames` frames touches when it starts `filled` frames into an integration of A
+size_t spec_subblocks(size_t filled, size_t A, size_t frames);
+hipError_t launch_spec(bool f64, const SpecArgs& a, hipStream_t s);
+
 // batched DotProduct::execute
 struct DotArgs {
     const void* coefs;

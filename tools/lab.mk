@@ -35,4 +35,12 @@ tools/_build/lab/ols_lab.o: HIPFLAGS += -mllvm -amdgpu-kernarg-preload-count=$(O
 $(OUT): $(patsubst %,tools/_build/lab/%.o,$(LAB_TUS)) $(PRODUCT_OBJS)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@.tmp $^ && mv -f $@.tmp $@
 
-.PHONY: all
+# the product with kern_spec.hip's sub-blocks cut at 31 frames: numerically wrong on purpose, for one
+# run of tests/test_gpu_spec.py (profiles/r21/LAB.md).   make -f tools/lab.mk spec_cut31
+SPEC_CUT31 = tools/_build/libsdsp_spec_cut31.so
+spec_cut31: $(SPEC_CUT31)
+tools/_build/lab/spec_cut31.o: $(CSRC)/kern_spec.hip
+$(SPEC_CUT31): tools/_build/lab/spec_cut31.o $(filter-out $(OBJ)/kern_spec.o,$(wildcard $(OBJ)/*.o))
+	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@.tmp $^ && mv -f $@.tmp $@
+
+.PHONY: all spec_cut31
